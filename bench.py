@@ -7,7 +7,15 @@ A "step" is one complete numeric factorization (assembly, POTRF/TRSM, SYRK,
 extend-add of every front) with A's values already resident in HBM.
 GFLOP/s = F / step time, F = sum_j colcount[j]^2 (algorithmic).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--k 128]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--k 128] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line (with
+the roofline figures of the dominant kernel, which are stamped inside the timed
+steps and take no run of their own).  --full adds what takes runs of its own after
+the timed steps: the validation of the timed factor by a GPU solve (backward error),
+the solve timing and the CPU baseline.  --dump-outputs DIR writes a fixed sample of
+the columns of the factor the last timed step left (what Numeric.export_cols hands
+a caller) as DIR/<name>.npy.
 
 N > 1 is launched by torch.distributed.run (one rank per GPU): the assembly
 tree is partitioned by subtrees over the ranks; contribution blocks move over
@@ -151,14 +159,75 @@ def backward_error(A, x, b):
     return float(r / (anorm.max() * np.abs(x).max() + np.abs(b).max()))
 
 
+# --dump-outputs: runs of DUMP_RUN consecutive columns of L, DUMP_TOP_RUNS of them drawn
+# from the last DUMP_TOP columns (the top separators of an ND order, where nearly all the
+# flops are), DUMP_ALL_RUNS from all columns, and the last DUMP_TAIL columns (the end of
+# the root).  The draw depends on n and the seed only.
+DUMP_SEED = 20261019
+DUMP_RUN = 8
+DUMP_TOP = 262144
+DUMP_TOP_RUNS = 24
+DUMP_ALL_RUNS = 96
+DUMP_TAIL = 256
+DUMP_MAX_BYTES = 28 << 20  # of float64 values; with as many row indices the dump stays below 64 MB
+
+
+def dump_columns(n):
+    """Sorted, disjoint column ranges [j0, j1) of the --dump-outputs sample."""
+    rng = np.random.default_rng(DUMP_SEED)
+    tail = min(DUMP_TAIL, n)
+    span = max(n - tail - DUMP_RUN, 1)
+    top0 = max(span - DUMP_TOP, 0)
+    starts = set(int(x) for x in rng.integers(top0, span, DUMP_TOP_RUNS))
+    starts |= set(int(x) for x in rng.integers(0, span, DUMP_ALL_RUNS))
+    runs, end = [], 0
+    for j0 in sorted(starts):
+        j0 = max(j0, end)
+        end = min(j0 + DUMP_RUN, n - tail)
+        if end > j0:
+            runs.append((j0, end))
+    runs.append((n - tail, n))
+    return runs
+
+
+def dump_outputs(num, n, out_dir):
+    """Writes the sampled columns of the factor held by `num`: L_columns.npy (the column
+    indices), L_colptr.npy (column c's entries are L_values[colptr[c]:colptr[c+1]], from
+    the diagonal down, explicit zeros of relaxed supernodes included), L_rows.npy and
+    L_values.npy, all float64 (the integers are exact).  Columns past DUMP_MAX_BYTES of
+    values are dropped from the end of the sample, so the same build writes the same
+    columns every run."""
+    os.makedirs(out_dir, exist_ok=True)
+    cols, ptr, rows, vals, tot = [], [0], [], [], 0
+    for j0, j1 in dump_columns(n):
+        cp, ri, rx = num.export_cols(j0, j1)
+        if (tot + len(rx)) * 8 > DUMP_MAX_BYTES:
+            break
+        cols.append(np.arange(j0, j1, dtype=np.float64))
+        ptr.extend((cp[1:] + tot).tolist())
+        rows.append(ri.astype(np.float64))
+        vals.append(rx)
+        tot += len(rx)
+    arrays = {"L_columns": np.concatenate(cols), "L_colptr": np.asarray(ptr, dtype=np.float64),
+              "L_rows": np.concatenate(rows), "L_values": np.concatenate(vals)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: int(a.size) for name, a in arrays.items()}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--k", type=int, default=128)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-solve", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also validate the timed factor (GPU solve, backward error), "
+                         "time the solve and run the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write a fixed sample of the columns of the last timed step's factor as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
+    ap.add_argument("--no-solve", action="store_true", help="with --full: leave the solve timing out")
     ap.add_argument("--cpu-k", type=int, default=32)
     ap.add_argument("--graph", type=int, default=1)
     ap.add_argument("--relax-wmax", type=int, default=None)
@@ -174,6 +243,10 @@ def main():
                          "through host memory over gloo (rehearsal with several ranks on one GPU); dry: "
                          "comm steps move nothing (per-rank compute only, the factor is not validated)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs is not None and (args.gpus > 1 or args.transport == "dry"):
+        ap.error("--dump-outputs writes the factor of a single-GPU run")
 
     import torch
     import sparsecholesky_amd as sc
@@ -303,6 +376,8 @@ def main():
                               "cb_all_tflops": round(cfl / (cms * 1e-3) / 1e12, 2)}
 
     mem = num.memory()  # before the solve allocates its buffers (and, multi-rank, the gathered factor)
+    # the factor of the last timed step, before anything else touches the handle
+    dumped = dump_outputs(num, st["n"], args.dump_outputs) if args.dump_outputs is not None else None
     # Validation of the factor just timed (outside the timed region): x = A^-1 b by
     # the GPU triangular solves with that factor (multi-rank handles gather
     # the factor collectively first), then the normwise backward error on the host,
@@ -310,8 +385,9 @@ def main():
     # A wrong factor cannot pass: the bound is 1e-12 (measured 6.9e-16 at 128^3).
     solve = None
     berr = None
-    skip = "skipped: dry transport (no data moved, factor not valid)"
-    validate = args.transport != "dry"
+    skip = ("skipped: dry transport (no data moved, factor not valid)" if args.full else
+            "skipped: plain run (--full validates the timed factor)")
+    validate = args.full and args.transport != "dry"
     if world > 1 and validate:
         # the multi-rank solve gathers the whole factor on every rank: when rehearsal
         # ranks share one GPU, check (collectively, so all ranks take the same branch)
@@ -339,7 +415,7 @@ def main():
         berr = backward_error(A, x, np.ones(st["n"]))
         if not berr < 1e-12:
             raise SystemExit(f"validation failed: backward error {berr:.3e} of the timed factor")
-    if world == 1 and not args.no_solve:
+    if args.full and world == 1 and not args.no_solve:
         # solve timing: forward + backward sweep, each reads L once (8 * panel entries
         # bytes, relaxed zeros included)
         reps = 3
@@ -395,7 +471,9 @@ def main():
                              "note": "rank 0 of the handle, factorization only (solve buffers excluded)"},
         "solve": solve,
     }
-    if not args.no_cpu_baseline and rank == 0 and world == 1:
+    if dumped is not None:
+        out["dumped"] = dumped
+    if args.full and not args.no_cpu_baseline and rank == 0 and world == 1:
         out["cpu_baseline"] = cpu_baseline(args.cpu_k)
     if rank == 0:
         print(json.dumps(out), flush=True)

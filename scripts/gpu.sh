@@ -19,6 +19,8 @@ cd "$GRAFT_REPO_ROOT"
 mkdir -p gpurun_out
 export TMPDIR=/tmp
 task=$1; shift || true
+OUT=${OUT:-out}  # where the suite and profile tasks write
+mkdir -p "$OUT"
 bench_line() {  # $1 = log file; prints the summary of its JSON line
   grep '^{' "$1" | tail -1 | python3 scripts/summarize.py
 }
@@ -26,18 +28,18 @@ case "$task" in
   suite)
     if [ -n "$1" ]; then SEL=(-k "$1"); else SEL=(); fi
     timeout -k 10 900 python -u -m pytest tests -m gpu -x -v -rP --timeout 300 --timeout-method thread \
-      -p no:cacheprovider "${SEL[@]}" > gpurun_out/pytest_gpu.log 2>&1
-    rc=$?; echo "pytest rc=$rc"; tail -5 gpurun_out/pytest_gpu.log
+      -p no:cacheprovider "${SEL[@]}" > "$OUT/pytest_gpu.log" 2>&1
+    rc=$?; echo "pytest rc=$rc"; tail -5 "$OUT/pytest_gpu.log"
     [ $rc -ne 0 ] && exit $rc
-    timeout -k 10 300 python -u bench.py --steps 5 --warmup 2 > gpurun_out/bench.json 2> gpurun_out/bench.err
-    rc=$?; echo "bench rc=$rc"; cat gpurun_out/bench.json
+    timeout -k 10 300 python -u bench.py --full --steps 5 --warmup 2 > "$OUT/bench.json" 2> "$OUT/bench.err"
+    rc=$?; echo "bench rc=$rc"; cat "$OUT/bench.json"
     exit $rc ;;
   profile)
-    timeout -k 10 600 python bench.py > gpurun_out/bench_default.log 2>&1 || exit $?
-    bench_line gpurun_out/bench_default.log
-    timeout -k 10 600 rocprofv3 --kernel-trace --stats -f csv -d gpurun_out/prof -o bench -- \
-      python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline > gpurun_out/bench_prof.log 2>&1 || exit $?
-    ls gpurun_out/prof ;;
+    timeout -k 10 600 python bench.py --full > "$OUT/bench_default.log" 2>&1 || exit $?
+    bench_line "$OUT/bench_default.log"
+    timeout -k 10 600 rocprofv3 --kernel-trace --stats -f csv -d "$OUT/prof" -o bench -- \
+      python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline > "$OUT/bench_prof.log" 2>&1 || exit $?
+    ls "$OUT/prof" ;;
   pmc)
     # FETCH_SIZE and WRITE_SIZE do not fit one pass on gfx950: one pass each, kernel
     # trace only, on an eager step so every dispatch is attributed
@@ -68,7 +70,7 @@ case "$task" in
     for rep in 1 2; do
       for spec in "$@"; do
         v=${spec%%@*}
-        opts=()
+        opts=(--full)  # the lines below print the validation's backward error
         if [ "$spec" != "$v" ]; then
           IFS='@' read -ra kv <<< "${spec#*@}"
           for o in "${kv[@]}"; do opts+=(--opt "$o"); done
@@ -83,7 +85,7 @@ case "$task" in
     for rep in 1 2; do
       for spec in "$@"; do
         v=${spec%%@*}
-        opts=()
+        opts=(--full)  # the lines below print the validation's backward error
         if [ "$spec" != "$v" ]; then
           IFS='@' read -ra kv <<< "${spec#*@}"
           for o in "${kv[@]}"; do opts+=(--opt "$o"); done
@@ -99,7 +101,7 @@ case "$task" in
     for n in $RANKS; do
       for tr in host dry; do
         timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 \
-          --master-port $((29500 + n)) bench.py --gpus $n --steps 3 --warmup 1 --k $K --transport $tr \
+          --master-port $((29500 + n)) bench.py --full --gpus $n --steps 3 --warmup 1 --k $K --transport $tr \
           > gpurun_out/rehearse_k${K}_n${n}_${tr}.log 2>&1 || { echo "rehearsal n=$n $tr failed"; tail -20 gpurun_out/rehearse_k${K}_n${n}_${tr}.log; exit 1; }
         grep '^{' gpurun_out/rehearse_k${K}_n${n}_${tr}.log | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print($n, '$tr', d['n_gpus'], d['ms_per_step'], d['value'], d['validation']['backward_error'], d['config']['work_share_per_rank'])"
       done

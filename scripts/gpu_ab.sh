@@ -4,7 +4,7 @@
 export TMPDIR=/tmp; mkdir -p gpurun_out
 for rep in 1 2; do
   for spec in "$@"; do
-    opts=()
+    opts=(--full)  # the validation's backward error is printed below
     if [ "$spec" != "base" ]; then IFS=',' read -ra kv <<< "$spec"; for o in "${kv[@]}"; do opts+=(--opt "$o"); done; fi
     tag=$(echo "$spec" | tr '=,' '__')
     timeout -k 10 300 python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-solve "${opts[@]}" > gpurun_out/ab_$tag.log 2>&1 || { tail -5 gpurun_out/ab_$tag.log; exit 1; }
