@@ -51,6 +51,20 @@ int64_t sc_debug_hwid(int32_t nwg, int32_t threads, int32_t spin_ticks, uint32_t
 int64_t sc_debug_contention(int32_t M, int32_t K, int32_t chain_rows, int32_t nchain, int32_t mode,
                             int32_t mask_stride, double* out);
 
+/* Digest of the launch schedule a handle would build, planned on the host (no device
+ * needed): nranks == 1 and emulate == 0 as sc_numeric_create; otherwise as a multi-rank
+ * handle of `rank` (emulate 0), or of every rank in one process with transfers as device
+ * copies (1) or RCCL to self (2).  out[0] = a 64-bit hash of every decoded schedule
+ * entry and every uploaded task array (pointers as arena + offset); then the entries
+ * per call kind (front small, chain, tiny tree, tiny dense, assembly by columns / tiled
+ * / tiled with limits, POTRF, TRSM fused / prefactored / partial, SYRK panel / CB, comm,
+ * record, wait); then tail-split launches, pre-factor launches, comm steps, events,
+ * messages and gather segments.  Writes at most cap values, returns their number. */
+int64_t sc_debug_schedule_digest(const sc_symbolic* sym, int32_t nranks, int32_t rank, int32_t emulate,
+                                 int64_t* out, int64_t cap);
+/* The same digest of a live handle, hashed at creation from what it uploaded. */
+int64_t sc_debug_numeric_digest(const sc_numeric* num, int64_t* out, int64_t cap);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

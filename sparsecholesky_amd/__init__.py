@@ -158,7 +158,23 @@ _SIGS = [
     ("sc_debug_solve_eager", _I64, [_P, _I32]),
     ("sc_debug_hwid", _I64, [_I32, _I32, _I32, _P]),
     ("sc_debug_contention", _I64, [_I32, _I32, _I32, _I32, _I32, _I32, _P]),
+    ("sc_debug_schedule_digest", _I64, [_P, _I32, _I32, _I32, _P, _I64]),
+    ("sc_debug_numeric_digest", _I64, [_P, _P, _I64]),
 ]
+
+# decoded call kinds of a schedule entry, in the order of the digest's counters
+CALL_KINDS = ("front_small", "chain", "tiny_tree", "tiny_dense", "asm_cols", "asm_tiled", "asm_tiled_lim", "potrf",
+              "trsm_fused", "trsm_pre", "trsm_partial", "syrk_panel", "syrk_cb", "comm", "record", "wait")
+_DIGEST_COUNTERS = ("tail_split", "pf", "comm_steps", "events", "msgs", "gsegs")
+
+
+def _digest_dict(call, what):
+    n = len(CALL_KINDS) + len(_DIGEST_COUNTERS) + 1
+    v = np.zeros(n, dtype=np.int64)
+    assert _check(call(_ptr(v), n), what) == n
+    d = {"hash": "%016x" % (int(v[0]) & (2 ** 64 - 1)), "calls": dict(zip(CALL_KINDS, v[1:].tolist()))}
+    d.update(zip(_DIGEST_COUNTERS, v[1 + len(CALL_KINDS):].tolist()))
+    return d
 
 _lib: Optional[C.CDLL] = None
 
@@ -529,6 +545,14 @@ class Symbolic:
         _check(lib().sc_memory_plan(self.h, nranks, _ptr(pb), _ptr(wb), _ptr(lb)), "memory_plan")
         return dict(panel=pb, work=wb, work_lower_bound=lb)
 
+    def schedule_digest(self, nranks: int = 1, rank: int = 0, emulate: int = 0) -> dict:
+        """Digest of the launch schedule a :class:`Numeric` of this analysis would build, computed
+        on the host (no GPU): ``hash`` (hex) over every decoded launch and every uploaded task
+        array, ``calls`` per kind (:data:`CALL_KINDS`) and the counters.  ``emulate``: 0 one real
+        rank, 1 every rank in this process (``virtual=True``), 2 the same with ``rccl_self=True``."""
+        return _digest_dict(lambda out, n: lib().sc_debug_schedule_digest(self.h, nranks, rank, emulate, out, n),
+                            "schedule_digest")
+
     def dist_steps(self, nranks: int) -> dict:
         """The plan's comm steps in order: kind (0 INIT, 1 SLAB, 2 DELIVER), level, front,
         slab / column group k and slab piece p."""
@@ -649,6 +673,11 @@ class Numeric:
         v = np.zeros(4, dtype=np.int64)
         _check(lib().sc_numeric_memory(self.h, _ptr(v), 4), "memory")
         return dict(total=int(v[0]), panel=int(v[1]), work=int(v[2]), work_lower_bound=int(v[3]))
+
+    def schedule_digest(self) -> dict:
+        """The digest (:meth:`Symbolic.schedule_digest`) of this handle's schedule, hashed at
+        creation from what was uploaded."""
+        return _digest_dict(lambda out, n: lib().sc_debug_numeric_digest(self.h, out, n), "numeric_digest")
 
     @property
     def stream(self) -> int:

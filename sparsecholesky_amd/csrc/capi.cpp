@@ -360,6 +360,28 @@ int64_t sc_debug_chain_stamps(sc_numeric* num, int32_t enable, uint64_t* out, in
     return sc::numeric_chain_stamps(*num->N, enable, out, cap);
 }
 
+static int64_t digest_out(const sc::SchedDigest& d, int64_t* out, int64_t cap) {
+    int64_t v[sc::SchedDigest::NVALS] = {(int64_t)d.hash};
+    for (int c = 0; c < sc::C_KINDS; ++c) v[1 + c] = d.calls[c];
+    const int64_t rest[6] = {d.tail_split, d.pf, d.comm_steps, d.events, d.msgs, d.gsegs};
+    std::copy(rest, rest + 6, v + 1 + sc::C_KINDS);
+    if (out) std::copy(v, v + std::min<int64_t>(cap, sc::SchedDigest::NVALS), out);
+    return sc::SchedDigest::NVALS;
+}
+
+int64_t sc_debug_schedule_digest(const sc_symbolic* sym, int32_t nranks, int32_t rank, int32_t emulate, int64_t* out,
+                                 int64_t cap) {
+    if (!sym || cap < 0) return SC_ERR_ARG;
+    sc::SchedDigest d;
+    const int64_t rc = sc::schedule_digest_host(sym->S, nranks, rank, emulate, d, g_last_error);
+    return rc != SC_OK ? rc : digest_out(d, out, cap);
+}
+
+int64_t sc_debug_numeric_digest(const sc_numeric* num, int64_t* out, int64_t cap) {
+    if (!num || !num->N || cap < 0) return SC_ERR_ARG;
+    return digest_out(num->N->digest, out, cap);
+}
+
 void sc_free_numeric(sc_numeric* num) {
     if (!num) return;
     sc::numeric_free(num->N);

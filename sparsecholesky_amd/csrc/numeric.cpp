@@ -71,25 +71,67 @@ static void panel_layout(Numeric& N, const Symbolic& S, int nranks) {
     }
 }
 
-int64_t numeric_init(Numeric& N, const Symbolic& S, int device) {
+int64_t numeric_plan_host(Numeric& N, const Symbolic& S) {
     N.S = &S;
-    auto fail = [&](int64_t rc) { return rc; };
+    static_assert(ASM_ROWS == kAsmRows, "assembly row tile");
+    static_assert(ASM_COLS == kAsmCols, "assembly column block");
+    for (int32_t s = 0; s < S.ns; ++s)
+        if (S.sn_m[s] >= (1 << 20)) {  // assembly task encoding: 16-bit column block index
+            N.err = "front with >= 2^20 rows is not supported";
+            return SC_ERR_NOTIMPL;
+        }
+    // a process hosts one rank, or every rank when emulated
+    const bool multi = !N.owner.empty();
+    N.R.clear();
+    N.R.resize(multi && N.emulated ? (size_t)N.nranks : 1);
+    for (size_t v = 0; v < N.R.size(); ++v) {
+        const int r = (multi && N.emulated) ? (int)v : (multi ? N.rank : 0);
+        plan_rank_memory(S, multi ? &N.D : nullptr, r, N.R[v]);
+    }
+    panel_layout(N, S, multi ? N.nranks : 1);
+    return SC_OK;
+}
+
+void set_pool_bases(Numeric& N, double* pbase, double* wbase) {
+    int64_t po = 0, wo = 0;
+    for (RankMem& R : N.R) {
+        R.P.panel_pool = pbase + po;
+        R.P.cb_pool = wbase + wo;
+        po += R.panel_total;
+        wo += R.work_total;
+    }
+}
+
+void finish_build(Numeric& N, SchedBuild& B, double* staging) {
+    CommBuild& cb = B.cb;
+    if (cb.stage_total > 0) {
+        N.staging = staging;
+        for (size_t q = 0; q < N.msgs.size(); ++q) {
+            if (cb.msg_slot[q] >= 0) N.msgs[q].buf = staging + cb.msg_slot[q];
+            if (cb.msg_src_slot[q] >= 0) N.msgs[q].src_buf = staging + cb.msg_src_slot[q];
+        }
+        for (size_t q = 0; q < cb.copies.size(); ++q) cb.copies[q].b = staging + cb.copy_slot[q];
+    }
+    B.asml.resize(B.asmv.size(), make_int2(0, INT32_MAX));
+}
+
+int64_t numeric_init(Numeric& N, const Symbolic& S, int device) {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
         N.err = "no HIP device available";
-        return fail(SC_ERR_HIP);
+        return SC_ERR_HIP;
     }
     if (device < 0) {
         if (hipGetDevice(&device) != hipSuccess) device = 0;
     }
     if (device >= ndev) {
         N.err = "device index out of range";
-        return fail(SC_ERR_ARG);
+        return SC_ERR_ARG;
     }
     N.device = device;
     if (hipSetDevice(device) != hipSuccess) {
         N.err = "hipSetDevice failed";
-        return fail(SC_ERR_HIP);
+        return SC_ERR_HIP;
     }
     const bool multi = !N.owner.empty();
     // critical path (assembly, POTRF/TRSM chain, next-slab updates) on the high
@@ -104,32 +146,11 @@ int64_t numeric_init(Numeric& N, const Symbolic& S, int device) {
     if (ok && multi) ok = hipStreamCreateWithPriority(&N.stream3, hipStreamNonBlocking, prio_hi) == hipSuccess;
     if (!ok) {
         N.err = "hipStreamCreate failed";
-        return fail(SC_ERR_HIP);
+        return SC_ERR_HIP;
     }
     N.use_graph = S.opt.use_graph != 0;
-    const int32_t ns = S.ns;
     int64_t rc;
-    static_assert(ASM_ROWS == kAsmRows, "assembly row tile");
-    static_assert(ASM_COLS == kAsmCols, "assembly column block");
-    for (int32_t s = 0; s < S.ns; ++s)
-        if (S.sn_m[s] >= (1 << 20)) {  // assembly task encoding: 16-bit column block index
-            N.err = "front with >= 2^20 rows is not supported";
-            return fail(SC_ERR_NOTIMPL);
-        }
-    // ---- memory plan of the hosted ranks ----
-    N.R.clear();
-    if (!multi) {
-        N.R.resize(1);
-    } else if (N.emulated) {
-        N.R.resize((size_t)N.nranks);
-    } else {
-        N.R.resize(1);
-    }
-    for (size_t v = 0; v < N.R.size(); ++v) {
-        const int r = (multi && N.emulated) ? (int)v : (multi ? N.rank : 0);
-        plan_rank_memory(S, multi ? &N.D : nullptr, r, N.R[v]);
-    }
-    panel_layout(N, S, multi ? N.nranks : 1);
+    if ((rc = numeric_plan_host(N, S))) return rc;  // memory plan of the hosted ranks
     // ---- shared plan arrays ----
     DevPlan P0 {};
     int32_t *d_sn_start, *d_sn_m, *d_child_ptr, *d_child_list, *d_relind, *d_apos, *d_relbnd, *d_colbnd, *d_tilebnd;
@@ -142,7 +163,7 @@ int64_t numeric_init(Numeric& N, const Symbolic& S, int device) {
         (rc = upload(N, S.tb_ptr, d_tbptr)) || (rc = upload(N, S.tile_bnd, d_tilebnd)) ||
         (rc = upload(N, S.a_ptr, d_aptr)) || (rc = upload(N, S.a_pos, d_apos)) ||
         (rc = upload(N, S.a_src, d_asrc)) || (rc = upload(N, N.gpo, N.d_gpo)))
-        return fail(rc);
+        return rc;
     P0.sn_start = d_sn_start;
     P0.sn_m = d_sn_m;
     P0.child_ptr = d_child_ptr;
@@ -159,13 +180,13 @@ int64_t numeric_init(Numeric& N, const Symbolic& S, int device) {
     P0.a_pos = d_apos;
     P0.a_src = d_asrc;
     void* p = nullptr;
-    if ((rc = dalloc(N, 64, p))) return fail(rc);
+    if ((rc = dalloc(N, 64, p))) return rc;
     N.d_info = (int32_t*)p;
     P0.info = N.d_info;
     if (hipHostMalloc((void**)&N.h_info, sizeof(int32_t) * 16, hipHostMallocMapped | hipHostMallocCoherent) !=
         hipSuccess) {
         N.err = "hipHostMalloc failed";
-        return fail(SC_ERR_NOMEM);
+        return SC_ERR_NOMEM;
     }
     // ---- pools: the hosted ranks' panel arenas back to back in one allocation (so an
     // emulated handle's allocation IS the gathered factor), work arenas likewise ----
@@ -174,68 +195,59 @@ int64_t numeric_init(Numeric& N, const Symbolic& S, int device) {
         ptot += R.panel_total;
         wtot += R.work_total;
     }
-    if ((rc = dalloc(N, (size_t)ptot * sizeof(double), p))) return fail(rc);
+    if ((rc = dalloc(N, (size_t)ptot * sizeof(double), p))) return rc;
     double* pbase = (double*)p;
-    if ((rc = dalloc(N, (size_t)std::max<int64_t>(wtot, 1) * sizeof(double), p))) return fail(rc);
+    if ((rc = dalloc(N, (size_t)std::max<int64_t>(wtot, 1) * sizeof(double), p))) return rc;
     double* wbase = (double*)p;
-    int64_t po = 0, wo = 0;
+    for (RankMem& R : N.R) R.P = P0;
+    set_pool_bases(N, pbase, wbase);
     for (RankMem& R : N.R) {
-        R.P = P0;
-        R.P.panel_pool = pbase + po;
-        R.P.cb_pool = wbase + wo;
-        po += R.panel_total;
-        wo += R.work_total;
         int64_t* dp = nullptr;
-        if ((rc = upload(N, R.panel_off, dp))) return fail(rc);
+        if ((rc = upload(N, R.panel_off, dp))) return rc;
         R.P.panel_off = dp;
         // the kernels address a CB as the full square from its (virtual) origin
         std::vector<int64_t> base((size_t)S.ns, 0);
         for (int32_t s = 0; s < S.ns; ++s)
             if (R.cb_off[s] >= 0) base[s] = R.cb_base(S, s);
-        if ((rc = upload(N, base, dp))) return fail(rc);
+        if ((rc = upload(N, base, dp))) return rc;
         R.P.cb_off = dp;
     }
     if (!multi || N.emulated) N.gpanel = pbase;  // gathered layout == the arenas
 
     SchedBuild B;
-    if ((rc = build_schedule(N, B))) return fail(rc);
+    if ((rc = build_schedule(N, B))) return rc;
     CommBuild& cbld = B.cb;
-    if (cbld.stage_total > 0) {  // multi-rank: packed staging slots of the hosted ranks' messages
-        if ((rc = dalloc(N, (size_t)cbld.stage_total * sizeof(double), p))) return fail(rc);
-        N.staging = (double*)p;
-        for (size_t q = 0; q < N.msgs.size(); ++q) {
-            if (cbld.msg_slot[q] >= 0) N.msgs[q].buf = N.staging + cbld.msg_slot[q];
-            if (cbld.msg_src_slot[q] >= 0) N.msgs[q].src_buf = N.staging + cbld.msg_src_slot[q];
-        }
-        for (size_t q = 0; q < cbld.copies.size(); ++q) cbld.copies[q].b = N.staging + cbld.copy_slot[q];
-    }
-    if ((rc = upload(N, cbld.copies, N.d_copy)) || (rc = upload(N, cbld.ctiles, N.d_ctiles))) return fail(rc);
+    // multi-rank: packed staging slots of the hosted ranks' messages
+    if (cbld.stage_total > 0 && (rc = dalloc(N, (size_t)cbld.stage_total * sizeof(double), p))) return rc;
+    finish_build(N, B, (double*)p);
+    N.digest = schedule_digest(N, B);  // of exactly what is uploaded below
+    if ((rc = upload(N, cbld.copies, N.d_copy)) || (rc = upload(N, cbld.ctiles, N.d_ctiles))) return rc;
     N.stamp_of.assign(N.sched.size(), -1);
     int nstamp = 0;
     for (size_t i = 0; i < N.sched.size(); ++i)
         if (N.sched[i].kind == L_CB) N.stamp_of[i] = nstamp++;
-    if ((rc = dalloc(N, (size_t)std::max(1, 2 * nstamp) * sizeof(uint64_t), p))) return fail(rc);
+    if ((rc = dalloc(N, (size_t)std::max(1, 2 * nstamp) * sizeof(uint64_t), p))) return rc;
     N.d_stamps = (uint64_t*)p;
     N.sync_ev.assign((size_t)N.n_sync_events, nullptr);
     for (auto& e : N.sync_ev)
         if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) {
             N.err = "hipEventCreate failed";
-            return fail(SC_ERR_HIP);
+            return SC_ERR_HIP;
         }
     {
         ChainDesc* dd = nullptr;
         uint32_t* dr = nullptr;
-        if ((rc = upload(N, B.cdesc, dd)) || (rc = upload(N, B.crelp, dr))) return fail(rc);
+        if ((rc = upload(N, B.cdesc, dd)) || (rc = upload(N, B.crelp, dr))) return rc;
         N.CP.desc = dd;
         N.CP.relp = dr;
         N.n_chain = (int64_t)B.cdesc.size();
-        if ((rc = dalloc(N, (size_t)std::max<int64_t>(B.chain_init, 1) * sizeof(double), p))) return fail(rc);
+        if ((rc = dalloc(N, (size_t)std::max<int64_t>(B.chain_init, 1) * sizeof(double), p))) return rc;
         N.CP.init = (double*)p;
         TinyFront* tf = nullptr;
         int2 *t1 = nullptr, *t2 = nullptr, *t3 = nullptr;
         if ((rc = upload(N, B.tfr, tf)) || (rc = upload(N, B.ta, t1)) || (rc = upload(N, B.tph, t2)) ||
             (rc = upload(N, B.tpr, t3)))
-            return fail(rc);
+            return rc;
         N.TP.fr = tf;
         N.TP.a = t1;
         N.TP.ph = t2;
@@ -250,11 +262,12 @@ int64_t numeric_init(Numeric& N, const Symbolic& S, int device) {
         // a tiny-tree handle is one launch: the kernel owns the status word (initial
         // value, failures, the copy to pinned host memory), so a factorization is one
         // dispatch with no reset / copy around it
-        if (N.sched.size() == 1 && N.sched[0].kind == L_SMALL && N.sched[0].big >= 2) {
+        const CallKind c0 = N.sched.size() == 1 ? decode_call(N.sched[0]) : C_KINDS;
+        if (c0 == C_TINY_TREE || c0 == C_TINY_DENSE) {
             void* dp = nullptr;
             if (hipHostGetDevicePointer(&dp, N.h_info, 0) != hipSuccess) {
                 N.err = "hipHostGetDevicePointer failed";
-                return fail(SC_ERR_HIP);
+                return SC_ERR_HIP;
             }
             N.TP.host_info = (int32_t*)dp;
         }
@@ -267,15 +280,14 @@ int64_t numeric_init(Numeric& N, const Symbolic& S, int device) {
         if (hipHostGetDevicePointer(&dp, N.h_info, 0) != hipSuccess || hipMemset(N.d_info, 0x7f, sizeof(int32_t)) != hipSuccess ||
             hipDeviceSynchronize() != hipSuccess) {
             N.err = "status word setup failed";
-            return fail(SC_ERR_HIP);
+            return SC_ERR_HIP;
         }
         N.status_dp = (int32_t*)dp;
     }
-    B.asml.resize(B.asmv.size(), make_int2(0, INT32_MAX));
     {  // the CB gather's segment tables
         int64_t* dgb = nullptr;
         GSeg* dgs = nullptr;
-        if ((rc = upload(N, B.gblk, dgb)) || (rc = upload(N, B.gseg, dgs))) return fail(rc);
+        if ((rc = upload(N, B.gblk, dgb)) || (rc = upload(N, B.gseg, dgs))) return rc;
         N.gtab.blk = dgb;
         N.gtab.seg = dgs;
     }
@@ -283,11 +295,9 @@ int64_t numeric_init(Numeric& N, const Symbolic& S, int device) {
         (rc = upload(N, B.potrf, N.d_potrf)) || (rc = upload(N, B.trsm, N.d_trsm)) ||
         (rc = upload(N, std::vector<int32_t>(B.trsm.size() + 1, 0), N.d_arrive)) ||
         (rc = upload(N, B.gemm, N.d_gemm)) || (rc = upload(N, B.tiles, N.d_tiles)))
-        return fail(rc);
-    (void)ns;
+        return rc;
     return SC_OK;
 }
-
 
 static hipStream_t stream_of(const Numeric& N, int strm) {
     return strm == 2 ? N.stream3 : strm == 1 ? N.stream2 : N.stream;
@@ -295,35 +305,45 @@ static hipStream_t stream_of(const Numeric& N, int strm) {
 
 static hipError_t launch_one(Numeric& N, const Launch& L, const double* d_Ax) {
     hipStream_t st = stream_of(N, L.strm);  // every kind on the stream its schedule entry names
-    switch (L.kind) {
-        case L_RECORD:
+    const DevPlan& P = N.R[L.vr].P;
+    const CallKind c = decode_call(L);
+    switch (c) {
+        case C_RECORD:
             return hipEventRecord(N.sync_ev[L.count], st);
-        case L_WAIT:
+        case C_WAIT:
             return hipStreamWaitEvent(st, N.sync_ev[L.count], 0);
-        case L_SMALL:
-            if (L.big == 1) return launch_front_chain(N.R[L.vr].P, N.CP, (int)L.off, L.count, L.maxm, d_Ax, st);
-            if (L.big == 2) return launch_tiny_tree(N.R[L.vr].P, N.TP, L.maxm, d_Ax, st);
-            if (L.big == 3) return launch_tiny_dense(N.R[L.vr].P, N.TP, L.maxm, d_Ax, st);
-            return launch_front_small(N.R[L.vr].P, N.d_small + L.off, L.count, L.maxm, false, d_Ax, st);
-        case L_ASM:
-            // epi = 1: distributed-assembly launch, column limits parallel to the tasks
-            return launch_assemble_large(N.R[L.vr].P, N.d_asm + L.off, L.count, d_Ax, st, L.big != 0,
-                                         L.epi ? N.d_asml + L.off : nullptr);
-        case L_POTRF:
-            return launch_potrf_diag(N.R[L.vr].P, N.d_potrf + L.off, L.count, st);
-        case L_TRSM:
-            return launch_trsm_panel(N.R[L.vr].P, N.d_trsm + L.off, L.count, st, L.big != 0, N.d_arrive,
-                                     L.epi);
-        case L_PANEL:
-        case L_CB:
+        case C_CHAIN:
+            return launch_front_chain(P, N.CP, (int)L.off, L.count, L.maxm, d_Ax, st);
+        case C_TINY_TREE:
+            return launch_tiny_tree(P, N.TP, L.maxm, d_Ax, st);
+        case C_TINY_DENSE:
+            return launch_tiny_dense(P, N.TP, L.maxm, d_Ax, st);
+        case C_FRONT_SMALL:
+            return launch_front_small(P, N.d_small + L.off, L.count, L.maxm, false, d_Ax, st);
+        case C_ASM_COLS:
+        case C_ASM_TILED:
+        case C_ASM_TILED_LIM:  // column limits parallel to the tasks
+            return launch_assemble_large(P, N.d_asm + L.off, L.count, d_Ax, st, c != C_ASM_COLS,
+                                         c == C_ASM_TILED_LIM ? N.d_asml + L.off : nullptr);
+        case C_POTRF:
+            return launch_potrf_diag(P, N.d_potrf + L.off, L.count, st);
+        case C_TRSM_FUSED:
+        case C_TRSM_PRE:
+        case C_TRSM_PARTIAL:
+            return launch_trsm_panel(P, N.d_trsm + L.off, L.count, st, c == C_TRSM_PARTIAL, N.d_arrive,
+                                     c == C_TRSM_PRE ? 2 : 0);
+        case C_SYRK_PANEL:
+        case C_SYRK_CB:
         {
             GatherTab gt = N.gtab;
             gt.info = N.d_info;
-            return launch_syrk(N.d_gemm + L.off, N.d_tiles + L.toff, L.count, L.bt, L.kind == L_CB ? 1 : 0, st, L.epi,
+            return launch_syrk(N.d_gemm + L.off, N.d_tiles + L.toff, L.count, L.bt, c == C_SYRK_CB ? 1 : 0, st, L.epi,
                                gt, L.lean != 0, L.pf != 0);
         }
-        case L_COMM:
+        case C_COMM:
             return comm_launch(N, L);
+        case C_KINDS:
+            break;
     }
     return hipErrorInvalidValue;
 }
@@ -605,7 +625,6 @@ int64_t numeric_syrk_stats(Numeric& N, int wmin, double* flops, double* ms, int6
     if (launches) *launches = cnt;
     return SC_OK;
 }
-
 
 void numeric_free(Numeric* Np) {
     if (!Np) return;

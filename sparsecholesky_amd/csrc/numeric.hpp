@@ -157,14 +157,20 @@ struct Msg {
     int32_t op;       // MsgOp
 };
 
+// Which kernel instance a launch of its kind uses (Launch::var), in CallKind order.
+enum SmallVar : int32_t { SMALL_FRONTS = 0, SMALL_CHAIN, SMALL_TINY_TREE, SMALL_TINY_DENSE };
+enum AsmVar : int32_t { ASM_BY_COLS = 0, ASM_TILED, ASM_TILED_LIM };
+enum TrsmVar : int32_t { TRSM_FUSED = 0, TRSM_PRE, TRSM_PARTIAL };
+
 struct Launch {
     int32_t kind;
+    int32_t var;      // L_SMALL: SmallVar, L_ASM: AsmVar, L_TRSM: TrsmVar; 0 for the other kinds
     int32_t level;
     int64_t off;      // first task in the kind's task array
     int64_t toff;     // first tile in the SYRK tile list
-    int32_t count;    // grid size (tiles for SYRK launches)
+    int32_t count;    // grid size (tiles for SYRK launches; the event of L_RECORD / L_WAIT)
     int32_t ntasks;   // tasks (SYRK launches)
-    int32_t maxm;     // small-front LDS edge
+    int32_t maxm;     // L_SMALL: LDS edge (tiny dense: n)
     int32_t big;      // CB launch covering fronts with w >= 256
     int32_t bt;       // SYRK tile edge (64 or 128)
     int32_t epi;      // SYRK instance tag: critical-path panel updates and short-K CB launches (profiles)
@@ -172,13 +178,62 @@ struct Launch {
     int32_t pf;       // panel update carrying pre-factor workgroups (GemmTask.pf; 64 x 64 tiles)
     int32_t strm;     // 0 = main stream, 1 = lookahead stream, 2 = comm stream
     int32_t vr;       // hosted rank whose DevPlan the kernel uses
-    double flops;     // algorithmic SYRK flops (CB launches: mb*(mb+1)*w)
+    double flops;     // algorithmic SYRK flops, 2 K per lower-trapezoid entry
     double bytes;     // algorithmic HBM bytes of a SYRK launch (numeric_syrk_bytes)
     // L_COMM: copy tiles [poff, poff + pcount) pack the sends, [uoff, uoff + ucount)
     // unpack the receives (Numeric::d_ctiles)
     int64_t poff, uoff;
     int32_t pcount, ucount;
     int32_t step;
+    int32_t tail;     // CB launch holding the re-cut last round of the launch before it (cb_tail_split)
+};
+
+// The call a schedule entry stands for: the launcher and the kernel instance it picks.
+// launch_one (numeric.cpp) dispatches on it and the schedule digest (digest.cpp) hashes
+// it, so the two cannot disagree.
+enum CallKind : int32_t {
+    C_FRONT_SMALL = 0,  // one workgroup per small front
+    C_CHAIN,            // a run of single-front levels in one workgroup
+    C_TINY_TREE,        // the whole tree in one workgroup
+    C_TINY_DENSE,       // the whole matrix in one wave
+    C_ASM_COLS,         // column-streaming assembly
+    C_ASM_TILED,        // write-once tile assembly
+    C_ASM_TILED_LIM,    // tile assembly with per-task column limits (distributed assembly)
+    C_POTRF,
+    C_TRSM_FUSED,       // full 64-column blocks, POTRF fused
+    C_TRSM_PRE,         // full blocks whose L11 is already in place
+    C_TRSM_PARTIAL,     // partial last blocks (nb < 64)
+    C_SYRK_PANEL,
+    C_SYRK_CB,
+    C_COMM,
+    C_RECORD,
+    C_WAIT,
+    C_KINDS
+};
+inline CallKind decode_call(const Launch& L) {
+    switch (L.kind) {
+        case L_SMALL: return CallKind(C_FRONT_SMALL + L.var);
+        case L_ASM: return CallKind(C_ASM_COLS + L.var);
+        case L_POTRF: return C_POTRF;
+        case L_TRSM: return CallKind(C_TRSM_FUSED + L.var);
+        case L_PANEL: return C_SYRK_PANEL;
+        case L_CB: return C_SYRK_CB;
+        case L_COMM: return C_COMM;
+        case L_RECORD: return C_RECORD;
+        case L_WAIT: return C_WAIT;
+    }
+    return C_KINDS;
+}
+
+// Digest of a schedule (digest.cpp): one hash over every decoded entry and every uploaded
+// task array (pointers as arena + offset), plus counters of what it issues.
+struct SchedDigest {
+    uint64_t hash = 0;
+    int64_t calls[C_KINDS] = {0};  // entries per CallKind
+    int64_t tail_split = 0;        // re-cut CB tail launches
+    int64_t pf = 0;                // panel updates carrying pre-factor workgroups
+    int64_t comm_steps = 0, events = 0, msgs = 0, gsegs = 0;
+    static constexpr int NVALS = 1 + C_KINDS + 6;
 };
 
 struct Numeric {
@@ -194,6 +249,7 @@ struct Numeric {
     std::vector<void*> allocs;
     int64_t dev_bytes = 0;           // device memory held (pools, plan, staging)
     std::vector<Launch> sched;
+    SchedDigest digest;              // of sched and the uploaded task arrays
     int32_t* d_small = nullptr;
     ChainPlan CP {};                 // chain launches (runs of single small-front levels)
     TinyPlan TP {};                  // tiny trees: the whole factorization in one workgroup
@@ -290,8 +346,17 @@ struct Numeric {
     std::string err;
 };
 
+// Host-only planning of a handle (no device needed): the hosted ranks (N.R), their
+// memory plans and the gathered panel layout.  N.rank / nranks / emulated / owner / D
+// are set by the caller.
+int64_t numeric_plan_host(Numeric& N, const Symbolic& S);
 // Builds the memory plan, pools and schedule of the hosted ranks.
 int64_t numeric_init(Numeric& N, const Symbolic& S, int device);
+// The digest of the schedule a handle created as numeric_create (nranks == 1, emulate ==
+// 0) or numeric_create_dist (emulate: 0 one real rank, 1 device copies, 2 RCCL to self)
+// would build, planned on the host with placeholder pool bases.  No HIP call.
+int64_t schedule_digest_host(const Symbolic& S, int nranks, int rank, int emulate, SchedDigest& out,
+                             std::string& err);
 
 int64_t numeric_create(const Symbolic& S, int device, Numeric*& out, std::string& err);
 int64_t numeric_factor(Numeric& N, const double* d_Ax, bool sync);

@@ -13,11 +13,11 @@
 
 namespace sc {
 
-// CB launches with every K below this use the batched SYRK epilogue (measured per
-// level at 128^3: K <= 121 gains, K = 226 loses)
-#ifndef SC_EPI_KMAX
-#define SC_EPI_KMAX 192
-#endif
+// CB launches with every K below this carry the short-K instance tag (Launch::epi).  The
+// tag only separates them in profiles: every SYRK instance stages its epilogue through LDS
+// (it once chose a batched epilogue: K <= 121 gained, K = 226 lost).
+// It also keeps them out of the CB tail re-cut.
+constexpr int SC_EPI_KMAX = 192;
 
 #define HIP_TRY(x)                                                                \
     do {                                                                          \
@@ -92,6 +92,12 @@ struct SchedBuild {
 // The static launch schedule of a handle (schedule.cpp): N.sched plus the task arrays
 // in B, final device addresses of the hosted ranks' pools.
 int64_t build_schedule(Numeric& N, SchedBuild& B);
+// The hosted ranks' panel and work arenas back to back from the two pool bases.
+void set_pool_bases(Numeric& N, double* pbase, double* wbase);
+// What remains once the staging pool exists: staging slots to addresses, column
+// limits for every assembly task.  B is then what numeric_init uploads.
+void finish_build(Numeric& N, SchedBuild& B, double* staging);
+SchedDigest schedule_digest(const Numeric& N, const SchedBuild& B);
 
 // dist.cpp
 hipError_t comm_launch(Numeric& N, const Launch& L);
