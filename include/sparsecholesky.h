@@ -34,7 +34,7 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define SC_VERSION 121 /* 1.2.1: small merged fronts amalgamated past relax_wmax (different supernode partition of some inputs, same L); 1.2.0: persistent slab chain options removed; panel_prefactor, dist_local_pieces and SC_ORDER_AMD added; out-of-range lookahead / inner_order / ordering rejected */
+#define SC_VERSION 121 /* still 1.2.1, additive: sc_solve_host_multi / sc_solve_device_multi (nrhs right-hand sides); 1.2.1:small merged fronts amalgamated past relax_wmax (different supernode partition of some inputs, same L); 1.2.0: persistent slab chain options removed; panel_prefactor, dist_local_pieces and SC_ORDER_AMD added; out-of-range lookahead / inner_order / ordering rejected */
 
 enum sc_status {
     SC_OK = 0,
@@ -273,6 +273,27 @@ void sc_free_numeric(sc_numeric* num);
  * gathers the whole factor onto every rank, then every rank solves. */
 int64_t sc_solve_host(sc_numeric* num, const double* b, double* x);
 int64_t sc_solve_device(sc_numeric* num, const double* d_b, double* d_x);
+/* X = A^-1 B for nrhs right-hand sides, column-major: column j of B at B + j*ldb (n
+ * entries used), of X at X + j*ldx; ldb, ldx >= n.  Any nrhs >= 0: the library works
+ * through it in panels of 16 columns (one read of L per sweep and panel instead of
+ * one per right-hand side); a last, partial panel is padded with zero columns inside
+ * the library, never read from or written to the caller's memory.  The result for a
+ * right-hand side is bitwise repeatable and does not depend on how many other
+ * columns travel with it or on its position.  These entry points always run the
+ * panel kernels, also for nrhs == 1; sc_solve_host / sc_solve_device keep their own
+ * kernels and their bits, so the two families agree to rounding, not bitwise.
+ * d_X may be d_B when ldx == ldb (in place).  Returns, ordering and collective rules
+ * are those of sc_solve_host / sc_solve_device: the factor's status (> 0: not positive
+ * definite, nothing solved, X untouched), SC_ERR_STATE before a factorization,
+ * collective on multi-rank handles, synchronous.  nrhs == 0 or n == 0: SC_OK, nothing
+ * touched.  SC_ERR_ARG (message in sc_last_error): num == NULL, nrhs < 0, ldb < n or
+ * ldx < n, a null B or X with nrhs > 0, X == B with ldx != ldb.  The first call
+ * allocates the panel work buffers (about 3 * 16 * 8 bytes per row plus the sweeps'
+ * scratch, counted in sc_numeric_memory info[0]); single-vector users never pay it. */
+int64_t sc_solve_device_multi(sc_numeric* num, int32_t nrhs, const double* d_B, int64_t ldb,
+                              double* d_X, int64_t ldx);
+int64_t sc_solve_host_multi(sc_numeric* num, int32_t nrhs, const double* B, int64_t ldb,
+                            double* X, int64_t ldx);
 
 /* ---------------- reference-API helpers (host) ----------------
  * Each mirrors one reference function, with int64 column pointers. */

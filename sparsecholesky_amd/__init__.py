@@ -128,6 +128,8 @@ _SIGS = [
     ("sc_free_numeric", None, [_P]),
     ("sc_solve_host", _I64, [_P, _P, _P]),
     ("sc_solve_device", _I64, [_P, _P, _P]),
+    ("sc_solve_device_multi", _I64, [_P, _I32, _P, _I64, _P, _I64]),
+    ("sc_solve_host_multi", _I64, [_P, _I32, _P, _I64, _P, _I64]),
     ("sc_etree", _I64, [_I64, _P, _P, _P]),
     ("sc_post_order", _I64, [_I64, _P, _P]),
     ("sc_col_count", _I64, [_I64, _P, _P, _P, _P, _P]),
@@ -703,7 +705,21 @@ class Numeric:
         return cp, ri[:tot], rx[:tot]
 
     def solve(self, b: np.ndarray) -> np.ndarray:
-        """x = A^{-1} b on the GPU (host vectors in / out)."""
+        """x = A^{-1} b on the GPU (host vectors in / out).  b of shape (n,): one solve
+        (sc_solve_host).  b of shape (n, k), any memory order: k right-hand sides through the
+        16-column panel solve (sc_solve_host_multi), returned as (n, k); its columns agree
+        with the 1-D solve to rounding, not bitwise."""
+        if np.ndim(b) == 2:
+            B = np.asfortranarray(b, dtype=np.float64)
+            n, k = B.shape
+            if n != self.symb.n:
+                raise ValueError(f"solve: b has {n} rows, the matrix {self.symb.n}")
+            X = np.zeros((n, k), dtype=np.float64, order="F")
+            ld = max(n, 1)
+            st = _check(lib().sc_solve_host_multi(self.h, k, _ptr(B), ld, _ptr(X), ld), "solve")
+            if st > 0:
+                raise LibraryError(f"solve: A is not positive definite (column {st})")
+            return X
         b = np.ascontiguousarray(b, dtype=np.float64)
         x = np.zeros_like(b)
         st = _check(lib().sc_solve_host(self.h, _ptr(b), _ptr(x)), "solve")
@@ -716,6 +732,15 @@ class Numeric:
         st = _check(lib().sc_solve_device(self.h, C.c_void_p(d_b_ptr), C.c_void_p(d_x_ptr)), "solve_device")
         if st > 0:
             raise LibraryError(f"solve_device: A is not positive definite (column {st})")
+        return st
+
+    def solve_device_multi(self, d_B_ptr: int, nrhs: int, ldb: int, d_X_ptr: int, ldx: int) -> int:
+        """X = A^{-1} B with device arrays, column-major: column j of B at d_B_ptr + 8 j ldb,
+        of X at d_X_ptr + 8 j ldx (ldb, ldx >= n; X may be B when ldx == ldb)."""
+        st = _check(lib().sc_solve_device_multi(self.h, nrhs, C.c_void_p(d_B_ptr), ldb, C.c_void_p(d_X_ptr), ldx),
+                    "solve_device_multi")
+        if st > 0:
+            raise LibraryError(f"solve_device_multi: A is not positive definite (column {st})")
         return st
 
     def __del__(self):

@@ -402,6 +402,42 @@ int64_t sc_solve_device(sc_numeric* num, const double* d_b, double* d_x) {
     return rc;
 }
 
+static int64_t solve_multi_args(sc_numeric* num, int32_t nrhs, const double* B, int64_t ldb, double* X,
+                                int64_t ldx, const char* what) {
+    const char* bad = nullptr;
+    const int64_t n = (num && num->N) ? num->N->S->n : 0;
+    if (!num || !num->N)
+        bad = "null handle";
+    else if (nrhs < 0)
+        bad = "nrhs < 0";
+    else if (ldb < n || ldx < n)
+        bad = "leading dimension below n";
+    else if (nrhs > 0 && (!B || !X))
+        bad = "null B or X";
+    else if (nrhs > 0 && (const double*)X == B && ldx != ldb)
+        bad = "X aliases B with ldx != ldb";
+    if (!bad) return SC_OK;
+    g_last_error = std::string(what) + ": " + bad;
+    return SC_ERR_ARG;
+}
+
+int64_t sc_solve_host_multi(sc_numeric* num, int32_t nrhs, const double* B, int64_t ldb, double* X, int64_t ldx) {
+    int64_t rc = solve_multi_args(num, nrhs, B, ldb, X, ldx, "sc_solve_host_multi");
+    if (rc != SC_OK) return rc;
+    rc = sc::numeric_solve_host_multi(*num->N, nrhs, B, ldb, X, ldx);
+    if (rc < 0) g_last_error = num->N->err;
+    return rc;
+}
+
+int64_t sc_solve_device_multi(sc_numeric* num, int32_t nrhs, const double* d_B, int64_t ldb, double* d_X,
+                              int64_t ldx) {
+    int64_t rc = solve_multi_args(num, nrhs, d_B, ldb, d_X, ldx, "sc_solve_device_multi");
+    if (rc != SC_OK) return rc;
+    rc = sc::numeric_solve_device_multi(*num->N, nrhs, d_B, ldb, d_X, ldx);
+    if (rc < 0) g_last_error = num->N->err;
+    return rc;
+}
+
 // ---- reference-API helpers ----
 int64_t sc_etree(int64_t n, const int64_t* Ap, const int32_t* Ai, int32_t* parent) {
     if (n < 0 || !Ap || !parent) return SC_ERR_ARG;

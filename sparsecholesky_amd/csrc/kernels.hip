@@ -2318,4 +2318,408 @@ hipError_t launch_permute(double* dst, const double* src, const int32_t* perm, i
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------
+// Panel solves: SOLVE_RHS = 16 right-hand sides at once, the same task lists and the
+// same stored block inverses as the single-vector kernels above.  c, y, u and part
+// hold 16-wide rows (entry (row, j) at 16 row + j), so every product is an
+// (rows x K) (K x 16) v_mfma_f64_16x16x4_f64 chain: A = L or X128 (lane: row lane & 15,
+// k = lane >> 4), B = the right-hand sides (k = lane >> 4, column lane & 15), D row
+// (lane >> 4) + 4 reg, column lane & 15.  A D column depends on its own B column only,
+// and every sum runs in a fixed order: a right-hand side's bits do not depend on what
+// travels with it or on its place in the panel.
+// ---------------------------------------------------------------------------
+constexpr int SOLVE_PANEL = SOLVE_NB * SOLVE_RHS;  // doubles of a 128 x 16 block of right-hand sides
+
+// Ys(128 x 16) = X128 Cs (TRANS: X128^T Cs) for the diagonal block at blk (nb columns),
+// Cs and Ys in LDS.  X128(i, k), k < i, sits at (row k, column i) of the block, the
+// diagonal as 1 / L(i, i); entries past nb and above the diagonal read as exact zeros
+// through the buffer's range check.  Four waves; wave v takes a short M tile (16 K steps:
+// tile v of the lower triangle, tile 7 - v of its transpose) and a long one (32 K steps:
+// tile 7 - v, or v), so the slot layout is static and the code small and branch-free
+// but for wave-uniform skips of 16-column groups past nb.  diag_load_multi issues every A
+// load (a kernel calls it first: the loads are on its critical path); diag_mfma_multi
+// runs the products.
+constexpr int DIAG_SLOTS = 48;  // K steps of a wave's two tiles
+constexpr int DIAG_SHORT = 16;
+struct DiagA {
+    double a[DIAG_SLOTS];
+    double d[2];  // L(i, i) of this lane's row in the short and the long tile
+};
+__device__ __forceinline__ int wave_id() { return __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); }
+
+template <bool TRANS>
+__device__ __forceinline__ void diag_load_multi(const double* __restrict__ blk, int m, int nb, DiagA& A) {
+    const int lane = threadIdx.x & 63, wv = wave_id();
+    const int il = lane & 15, kq = lane >> 4;
+    const __amdgpu_buffer_rsrc_t rs = buf_rsrc(blk, (uint32_t)(((int64_t)(nb - 1) * m + nb) * 8));
+    const int Is = TRANS ? 7 - wv : wv, Il = 7 - Is;
+#pragma unroll
+    for (int q = 0; q < DIAG_SLOTS; ++q) {
+        const int I = q < DIAG_SHORT ? Is : Il;
+        const int ks = q < DIAG_SHORT ? (TRANS ? 16 : 0) + q : q - DIAG_SHORT;
+        const int gi = 16 * I + il, gk = 4 * ks + kq;
+        // X128(gi, gk) (TRANS: X128(gk, gi)) = block entry (row = the smaller, column = the larger index)
+        const int hi = TRANS ? gk : gi, lw = TRANS ? gi : gk;
+        A.a[q] = buf_ld(rs, ((hi < nb) & (lw <= hi)) ? (hi * m + lw) * 8 : BUF_DEAD, 0);
+    }
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+        const int gi = 16 * (e ? Il : Is) + il;
+        A.d[e] = buf_ld(rs, gi < nb ? (gi * m + gi) * 8 : BUF_DEAD, 0);
+    }
+}
+
+template <bool TRANS>
+__device__ __forceinline__ void diag_mfma_multi(const DiagA& A, int nb, const double* Cs, double* Ys) {
+    const int lane = threadIdx.x & 63, wv = wave_id();
+    const int il = lane & 15, kq = lane >> 4;
+    const int Is = TRANS ? 7 - wv : wv, Il = 7 - Is;
+    double4_t acc[2] = {{0.0, 0.0, 0.0, 0.0}, {0.0, 0.0, 0.0, 0.0}};
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+        const int I = e ? Il : Is;
+        if (16 * I >= nb) continue;  // wave-uniform: the tile's rows are all past nb
+        const int gi = 16 * I + il;
+        const double dinv = gi < nb ? 1.0 / A.d[e] : 0.0;  // dead: 0, not 1/0
+#pragma unroll
+        for (int g = 0; g < (e ? DIAG_SLOTS - DIAG_SHORT : DIAG_SHORT) / 4; ++g) {
+            const int ks0 = (e ? 0 : (TRANS ? 16 : 0)) + 4 * g;
+            if (4 * ks0 >= nb) continue;  // wave-uniform: 16 columns past nb
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int gk = 4 * (ks0 + u) + kq;
+                const double av = gi == gk ? dinv : A.a[(e ? DIAG_SHORT : 0) + 4 * g + u];
+                acc[e] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, Cs[gk * SOLVE_RHS + il], acc[e], 0, 0, 0);
+            }
+        }
+    }
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        Ys[(16 * Is + kq + 4 * g) * SOLVE_RHS + il] = acc[0][g];
+        Ys[(16 * Il + kq + 4 * g) * SOLVE_RHS + il] = acc[1][g];
+    }
+}
+
+// Forward step of a panel: tasks as solve_fwd_kernel.  Y = X128 C_blk stays in LDS; wave
+// v forms ACC(64 x 16) = L(rows, blk) Y for rows r0 + 64 v .. (4 M tiles x 32 K steps,
+// each load four 128-byte runs; the second 64-column half of A goes out under the first
+// half's products) and subtracts it from c (rows < w) or the front's u.  The writer
+// stores Y to P.y.
+__global__ __launch_bounds__(SOLVE_ROWS) void solve_fwd_multi_kernel(SolvePlan P, const int4* __restrict__ tasks) {
+    __shared__ double Cs[SOLVE_PANEL], Ys[SOLVE_PANEL];
+    const int4 t = tasks[blockIdx.x];
+    const int s = t.x, k0 = t.y, r0 = t.z;
+    const int tid = threadIdx.x, lane = tid & 63, wv = wave_id();
+    const int il = lane & 15, kq = lane >> 4;
+    const int c0 = P.sn_start[s];
+    const int w = P.sn_start[s + 1] - c0;
+    const int m = P.sn_m[s];
+    const int nb = min(SOLVE_NB, w - k0);
+    const double* __restrict__ pan = P.panel_pool + P.panel_off[s] + (int64_t)k0 * m;
+    // the diagonal block's loads first (Y is on every row's critical path), then the first
+    // 64-column half of this wave's rows; the whole offset in the VGPR: the range check
+    // masks rows >= m and columns >= nb
+    DiagA xa;
+    diag_load_multi<false>(pan + k0, m, nb, xa);
+    const __amdgpu_buffer_rsrc_t rs = buf_rsrc(pan, (uint32_t)((int64_t)nb * m * 8));
+    const int rb = r0 + 64 * wv;  // this wave's rows
+    double a[2][4][PNB / 4];
+    auto load_half = [&](int h) {
+#pragma unroll
+        for (int ti = 0; ti < 4; ++ti)
+#pragma unroll
+            for (int ks = 0; ks < PNB / 4; ++ks) {
+                const int r = rb + 16 * ti + il, col = h * PNB + 4 * ks + kq;
+                a[h][ti][ks] = buf_ld(rs, ((r0 >= 0) & (r < m) & (col < nb)) ? (col * m + r) * 8 : BUF_DEAD, 0);
+            }
+    };
+    load_half(0);
+    const double* cblk = P.c + (int64_t)(c0 + k0) * SOLVE_RHS;
+#pragma unroll
+    for (int q = 0; q < SOLVE_PANEL / SOLVE_ROWS; ++q) {
+        const int e = tid + SOLVE_ROWS * q;
+        Cs[e] = (e >> 4) < nb ? cblk[e] : 0.0;
+    }
+    __syncthreads();
+    diag_mfma_multi<false>(xa, nb, Cs, Ys);
+    __syncthreads();
+    if (r0 >= 0 && nb > PNB) load_half(1);  // in flight under the first half's products
+    if (t.w) {
+        double* __restrict__ yblk = P.y + (int64_t)(c0 + k0) * SOLVE_RHS;
+#pragma unroll
+        for (int q = 0; q < SOLVE_PANEL / SOLVE_ROWS; ++q) {
+            const int e = tid + SOLVE_ROWS * q;
+            if ((e >> 4) < nb) yblk[e] = Ys[e];
+        }
+    }
+    if (r0 < 0) return;
+    double4_t acc[4];
+#pragma unroll
+    for (int ti = 0; ti < 4; ++ti) acc[ti] = double4_t {0.0, 0.0, 0.0, 0.0};
+    // tiles past m and 16-column groups past nb are skipped (wave-uniform; their A is all zeros)
+    auto mfma_half = [&](int h) {
+        double bv[PNB / 4];
+#pragma unroll
+        for (int ks = 0; ks < PNB / 4; ++ks) bv[ks] = Ys[(h * PNB + 4 * ks + kq) * SOLVE_RHS + il];
+#pragma unroll
+        for (int ti = 0; ti < 4; ++ti) {
+            if (rb + 16 * ti >= m) continue;
+#pragma unroll
+            for (int g = 0; g < PNB / 16; ++g) {
+                if (h * PNB + 16 * g >= nb) continue;
+#pragma unroll
+                for (int u = 0; u < 4; ++u)
+                    acc[ti] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[h][ti][4 * g + u], bv[4 * g + u], acc[ti], 0, 0, 0);
+            }
+        }
+    };
+    mfma_half(0);
+    if (nb > PNB) mfma_half(1);
+    // rows < w: this front's own later pivots; rows >= w: its contribution block's rows of
+    // u (one writer per row and step, as in solve_fwd_kernel); 16 lanes write one 128-byte row
+    const int32_t* __restrict__ rows = P.rows + P.rows_ptr[s];
+    double* __restrict__ us = P.u + P.u_off[s] * SOLVE_RHS;
+#pragma unroll
+    for (int ti = 0; ti < 4; ++ti)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const int r = rb + 16 * ti + kq + 4 * g;
+            if (r < m) {
+                double* dst = r < w ? P.c + (int64_t)rows[r] * SOLVE_RHS : us + (int64_t)(r - w) * SOLVE_RHS;
+                dst[il] -= acc[ti][g];
+            }
+        }
+}
+
+// Forward gather of a panel: solve_fwd_gather_kernel on 16-wide rows.  The columns are
+// independent, so a front's rows are split over GATHER_SPLIT workgroups of 4 columns
+// each (32-byte runs; the split keeps the serial walk over the children as short as the
+// single-vector kernel's).
+constexpr int GATHER_SPLIT = 4, GATHER_COLS = SOLVE_RHS / GATHER_SPLIT, GATHER_NT = 1024;
+__global__ __launch_bounds__(GATHER_NT) void solve_fwd_gather_multi_kernel(SolvePlan P,
+                                                                           const int32_t* __restrict__ fronts) {
+    const int s = fronts[blockIdx.x];
+    const int tid = threadIdx.x, j0 = GATHER_COLS * blockIdx.y;
+    const int c0 = P.sn_start[s];
+    const int w = P.sn_start[s + 1] - c0;
+    const int32_t* __restrict__ rows = P.rows + P.rows_ptr[s];
+    double* __restrict__ us = P.u + P.u_off[s] * SOLVE_RHS;
+    for (int q = P.child_ptr[s]; q < P.child_ptr[s + 1]; ++q) {
+        const int ch = P.child_list[q];
+        const int64_t r0 = P.rel_ptr[ch];
+        const int mbc = (int)(P.rel_ptr[ch + 1] - r0);
+        const double* __restrict__ uc = P.u + P.u_off[ch] * SOLVE_RHS;
+        const int32_t* __restrict__ rel = P.relind + r0;
+        __syncthreads();  // the previous child's adds are done
+        for (int e = tid; e < mbc * GATHER_COLS; e += GATHER_NT) {
+            const int i = e / GATHER_COLS, j = j0 + e % GATHER_COLS;
+            const int t = rel[i];
+            const double v = uc[(int64_t)i * SOLVE_RHS + j];
+            if (t < w)
+                P.c[(int64_t)rows[t] * SOLVE_RHS + j] += v;
+            else
+                us[(int64_t)(t - w) * SOLVE_RHS + j] += v;
+        }
+    }
+}
+
+// Backward step of a panel, part 1: workgroup (s, k0, r0) leaves its partial
+// P(128 x 16) = -L(rows, blk)^T X(rows) in part[task].  L is loaded as in
+// solve_gemv_kernel (thread = row, coalesced per column, all 128 columns in flight) and
+// transposed through LDS one 64-column half at a time, because in the MFMA layout the transposed operand would be
+// loaded in 32-byte runs.  Wave v owns rows r0 + 64 v ..: it reads back only what it
+// wrote (T[v]), holds its 64 rows of X as 16 B operands in registers, and the four
+// waves' 64 x 16 results are summed in wave order.
+constexpr int GEMV_LD = 64 + 4;  // column stride of T: 16 columns x 4 rows of an A read hit distinct banks
+__global__ __launch_bounds__(SOLVE_ROWS) void solve_gemv_multi_kernel(SolvePlan P, const int4* __restrict__ tasks) {
+    __shared__ double T[SOLVE_ROWS / 64][PNB][GEMV_LD];  // T[v][j][row] = L(r0 + 64 v + row, j)
+    static_assert(GEMV_LD >= SOLVE_RHS, "a wave's 64 x 16 result fits the start of its T[v]");
+    const int4 t = tasks[blockIdx.x];
+    const int s = t.x, k0 = t.y, r0 = t.z;
+    const int tid = threadIdx.x, lane = tid & 63, wv = wave_id();
+    const int il = lane & 15, kq = lane >> 4;
+    const int c0 = P.sn_start[s];
+    const int w = P.sn_start[s + 1] - c0;
+    const int m = P.sn_m[s];
+    const int nb = min(SOLVE_NB, w - k0);
+    const double* __restrict__ pan = P.panel_pool + P.panel_off[s] + (int64_t)k0 * m;
+    const int32_t* __restrict__ rows = P.rows + P.rows_ptr[s];
+    const int r = r0 + tid;
+    const bool live = r < m;
+    double bx[16];  // X(r0 + 64 v + 4 ks + kq, il); dead rows 0
+#pragma unroll
+    for (int ks = 0; ks < 16; ++ks) {
+        const int rr = r0 + 64 * wv + 4 * ks + kq;
+        bx[ks] = rr < m ? P.c[(int64_t)rows[rr] * SOLVE_RHS + il] : 0.0;
+    }
+    const __amdgpu_buffer_rsrc_t rs = buf_rsrc(pan, (uint32_t)((int64_t)nb * m * 8));
+    // both halves' loads go out at once (the second waits in registers)
+    double v[2][PNB];
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int q = 0; q < PNB; ++q) {
+            const int col = h * PNB + q;
+            v[h][q] = buf_ld(rs, (live & (col < nb)) ? (col * m + r) * 8 : BUF_DEAD, 0);
+        }
+    // R[v][j][16]: wave v's result, over the start of its own T[v] once its products are done
+    constexpr int W = PNB * GEMV_LD;
+    double* R = &T[0][0][0];
+    auto half = [&](int h) {
+#pragma unroll
+        for (int q = 0; q < PNB; ++q) T[wv][q][lane] = v[h][q];
+        __syncthreads();
+        double4_t acc[4];
+#pragma unroll
+        for (int I = 0; I < 4; ++I) acc[I] = double4_t {0.0, 0.0, 0.0, 0.0};
+        // tiles past nb and 16-row groups past m are skipped (wave-uniform; zeros)
+#pragma unroll
+        for (int I = 0; I < 4; ++I) {
+            if (h * PNB + 16 * I >= nb) continue;
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                if (r0 + 64 * wv + 16 * g >= m) continue;
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const int ks = 4 * g + u;
+                    acc[I] = __builtin_amdgcn_mfma_f64_16x16x4f64(T[wv][16 * I + il][4 * ks + kq], bx[ks], acc[I], 0, 0,
+                                                                  0);
+                }
+            }
+        }
+#pragma unroll
+        for (int I = 0; I < 4; ++I)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) R[wv * W + (16 * I + kq + 4 * g) * SOLVE_RHS + il] = acc[I][g];
+        __syncthreads();
+        double* __restrict__ out = P.part + ((int64_t)blockIdx.x * SOLVE_NB + h * PNB) * SOLVE_RHS;
+#pragma unroll
+        for (int q = 0; q < PNB * SOLVE_RHS / SOLVE_ROWS; ++q) {
+            const int e = tid + SOLVE_ROWS * q;
+            out[e] = -(R[e] + R[W + e] + R[2 * W + e] + R[3 * W + e]);  // in wave order
+        }
+    };
+    half(0);
+    if (nb > PNB) {
+        __syncthreads();  // the first half's R fully read
+        half(1);
+    }
+}
+
+// Backward step of a panel, part 2: C_blk plus the block's partials in task order, then
+// X_blk = X128^T C_blk.
+__global__ __launch_bounds__(256) void solve_diag_multi_kernel(SolvePlan P, const int4* __restrict__ tasks) {
+    __shared__ double Cs[SOLVE_PANEL], Ys[SOLVE_PANEL];
+    const int4 t = tasks[blockIdx.x];
+    const int s = t.x, k0 = t.y;
+    const int tid = threadIdx.x;
+    const int c0 = P.sn_start[s];
+    const int w = P.sn_start[s + 1] - c0;
+    const int m = P.sn_m[s];
+    const int nb = min(SOLVE_NB, w - k0);
+    const double* __restrict__ blk = P.panel_pool + P.panel_off[s] + (int64_t)k0 * m + k0;
+    double* __restrict__ cblk = P.c + (int64_t)(c0 + k0) * SOLVE_RHS;
+    DiagA xa;
+    diag_load_multi<true>(blk, m, nb, xa);
+    // C_blk plus the partials in task order, DIAG_PF tasks (x 8 entries per thread) in
+    // flight at a time; rows past nb stay 0 (dead parts of a partial are never read)
+    constexpr int NQ = SOLVE_PANEL / 256, DIAG_PF = 8;
+    double v[NQ];
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+        const int e = tid + 256 * q;
+        v[q] = (e >> 4) < nb ? cblk[e] : 0.0;
+    }
+    const double* __restrict__ part = P.part + (int64_t)t.z * SOLVE_PANEL;
+    for (int g0 = 0; g0 < t.w; g0 += DIAG_PF) {
+        double pv[DIAG_PF][NQ];
+#pragma unroll
+        for (int u = 0; u < DIAG_PF; ++u)
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) {
+                const int e = tid + 256 * q;
+                pv[u][q] = (g0 + u < t.w && (e >> 4) < nb) ? part[(int64_t)(g0 + u) * SOLVE_PANEL + e] : 0.0;
+            }
+#pragma unroll
+        for (int u = 0; u < DIAG_PF; ++u)
+            if (g0 + u < t.w) {
+#pragma unroll
+                for (int q = 0; q < NQ; ++q) v[q] += pv[u][q];
+            }
+    }
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) Cs[tid + 256 * q] = v[q];
+    __syncthreads();
+    diag_mfma_multi<true>(xa, nb, Cs, Ys);
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < SOLVE_PANEL / 256; ++q) {
+        const int e = tid + 256 * q;
+        if ((e >> 4) < nb) cblk[e] = Ys[e];
+    }
+}
+
+// c (16-wide rows, internal order) <- io (n x 16 column-major, caller's order) or back;
+// 64 rows per workgroup, transposed through LDS so both sides move in runs.
+__global__ __launch_bounds__(256) void permute_multi_kernel(double* __restrict__ c, double* __restrict__ io,
+                                                            const int32_t* __restrict__ perm, int64_t n, int scatter) {
+    __shared__ double tile[64][SOLVE_RHS + 1];
+    const int tid = threadIdx.x, il = tid & 63, jq = tid >> 6;
+    const int64_t i0 = (int64_t)blockIdx.x * 64, i = i0 + il;
+    const int64_t p = i < n ? perm[i] : 0;
+    if (!scatter) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) tile[il][jq + 4 * q] = i < n ? io[p + (jq + 4 * q) * n] : 0.0;
+    } else {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int e = tid + 256 * q;
+            tile[e >> 4][e & 15] = i0 + (e >> 4) < n ? c[i0 * SOLVE_RHS + e] : 0.0;
+        }
+    }
+    __syncthreads();
+    if (!scatter) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int e = tid + 256 * q;
+            if (i0 + (e >> 4) < n) c[i0 * SOLVE_RHS + e] = tile[e >> 4][e & 15];
+        }
+    } else if (i < n) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) io[p + (jq + 4 * q) * n] = tile[il][jq + 4 * q];
+    }
+}
+
+hipError_t launch_solve_fwd_multi(const SolvePlan& P, const int4* tasks, int count, hipStream_t st) {
+    if (count <= 0) return hipSuccess;
+    hipLaunchKernelGGL(solve_fwd_multi_kernel, dim3(count), dim3(SOLVE_ROWS), 0, st, P, tasks);
+    return hipGetLastError();
+}
+
+hipError_t launch_solve_fwd_gather_multi(const SolvePlan& P, const int32_t* fronts, int count, hipStream_t st) {
+    if (count <= 0) return hipSuccess;
+    hipLaunchKernelGGL(solve_fwd_gather_multi_kernel, dim3(count, GATHER_SPLIT), dim3(GATHER_NT), 0, st, P, fronts);
+    return hipGetLastError();
+}
+
+hipError_t launch_solve_gemv_multi(const SolvePlan& P, const int4* tasks, int count, hipStream_t st) {
+    if (count <= 0) return hipSuccess;
+    hipLaunchKernelGGL(solve_gemv_multi_kernel, dim3(count), dim3(SOLVE_ROWS), 0, st, P, tasks);
+    return hipGetLastError();
+}
+
+hipError_t launch_solve_diag_multi(const SolvePlan& P, const int4* tasks, int count, hipStream_t st) {
+    if (count <= 0) return hipSuccess;
+    hipLaunchKernelGGL(solve_diag_multi_kernel, dim3(count), dim3(256), 0, st, P, tasks);
+    return hipGetLastError();
+}
+
+hipError_t launch_permute_multi(double* c, double* io, const int32_t* perm, int64_t n, bool scatter,
+                                hipStream_t st) {
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(permute_multi_kernel, dim3((unsigned)((n + 63) / 64)), dim3(256), 0, st, c, io, perm, n,
+                       scatter ? 1 : 0);
+    return hipGetLastError();
+}
+
 }  // namespace sc

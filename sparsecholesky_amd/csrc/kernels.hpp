@@ -158,6 +158,19 @@ hipError_t launch_solve_diag(const SolvePlan& P, const int4* tasks, int count, h
 hipError_t launch_permute(double* dst, const double* src, const int32_t* perm, int64_t n, bool scatter,
                           hipStream_t st);
 
+// Panel solves (SOLVE_RHS right-hand sides at once): the same tasks with c, y, u and part
+// of the plan holding SOLVE_RHS-wide rows (entry (row, j) at SOLVE_RHS row + j; part:
+// SOLVE_NB x SOLVE_RHS per GEMV task); the products over the rows below a block run on
+// v_mfma_f64_16x16x4_f64.  launch_solve_inv is shared with the single-vector solve.
+constexpr int SOLVE_RHS = 16;
+hipError_t launch_solve_fwd_multi(const SolvePlan& P, const int4* tasks, int count, hipStream_t st);
+hipError_t launch_solve_fwd_gather_multi(const SolvePlan& P, const int32_t* fronts, int count, hipStream_t st);
+hipError_t launch_solve_gemv_multi(const SolvePlan& P, const int4* tasks, int count, hipStream_t st);
+hipError_t launch_solve_diag_multi(const SolvePlan& P, const int4* tasks, int count, hipStream_t st);
+// c[SOLVE_RHS i + j] = io[perm[i] + j n] (gather) or back (scatter); io: n x SOLVE_RHS column-major
+hipError_t launch_permute_multi(double* c, double* io, const int32_t* perm, int64_t n, bool scatter,
+                                hipStream_t st);
+
 // Small fronts (m <= maxm <= 128): one workgroup per front, factored in registers
 // (4 x 4 tiles per thread); seq: one workgroup runs the fronts in order (a whole
 // small tree in postorder, CBs through HBM).

@@ -342,6 +342,14 @@ struct Numeric {
     bool solve_eager = false;          // debug: launch the sweeps directly instead of the graph
     hipGraph_t solve_graph = nullptr;  // both sweeps captured once (b in / x out through d_sbuf)
     hipGraphExec_t solve_gexec = nullptr;
+    // panel solves (SOLVE_RHS right-hand sides): the plan's 16-wide buffers, allocated at
+    // the first multi solve, and the panel sweeps captured over d_mbuf's io panel
+    bool multi_ready = false;
+    SolvePlan SPM {};
+    int64_t solve_max_g = 1;           // most GEMV workgroups in one backward step
+    double* d_mbuf = nullptr;          // io (n x SOLVE_RHS column-major), c, y (SOLVE_RHS-wide rows)
+    hipGraph_t solve_multi_graph = nullptr;
+    hipGraphExec_t solve_multi_gexec = nullptr;
 
     std::string err;
 };
@@ -383,6 +391,13 @@ void numeric_free(Numeric* N);
 // (collective) and every rank solves with the whole factor.
 int64_t numeric_solve_device(Numeric& N, const double* d_b, double* d_x);
 int64_t numeric_solve_host(Numeric& N, const double* b, double* x);
+// X = A^{-1} B for nrhs right-hand sides, column-major (ldb, ldx >= n), in panels of
+// SOLVE_RHS columns through the panel kernels (also for nrhs == 1); a partial last panel
+// is padded with zero columns in the handle's own buffers.  d_X may be d_B when ldx ==
+// ldb.  Status, ordering and collective rules of numeric_solve_device.
+int64_t numeric_solve_device_multi(Numeric& N, int32_t nrhs, const double* d_B, int64_t ldb, double* d_X,
+                                   int64_t ldx);
+int64_t numeric_solve_host_multi(Numeric& N, int32_t nrhs, const double* B, int64_t ldb, double* X, int64_t ldx);
 int64_t debug_syrk(double* dC, int ldc, const double* dA, int lda, int M, int N, int K);
 int64_t numeric_chain_stamps(Numeric& N, int enable, uint64_t* out, int64_t cap);
 int64_t debug_bench(int which, int M, int K, int reps, int arg, double* tflops);

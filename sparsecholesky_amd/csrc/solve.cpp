@@ -183,6 +183,7 @@ static int64_t solve_build(Numeric& N) {
     N.u_total = u_tot;
     if ((rc = dalloc(N, (size_t)max_g * SOLVE_NB * sizeof(double), p))) return rc;
     N.SP.part = (double*)p;
+    N.solve_max_g = max_g;
     N.SP.u_off = d_u_off;
     N.SP.child_ptr = N.R[0].P.child_ptr;
     N.SP.child_list = N.R[0].P.child_list;
@@ -192,20 +193,32 @@ static int64_t solve_build(Numeric& N) {
     return SC_OK;
 }
 
-int64_t numeric_solve_device(Numeric& N, const double* d_b, double* d_x) {
-    if (!N.factored) return SC_ERR_STATE;
-    const int64_t st = numeric_status(N);
-    if (st != SC_OK) return st;
+// What both solves start with: the whole factor in gpanel (multi-rank: collective), the
+// plan built, and the captured sweeps dropped when they point at another panel pool.
+static int64_t solve_prepare(Numeric& N) {
     HIP_TRY(hipSetDevice(N.device));
     TRY(numeric_gather(N));  // multi-rank: every rank solves with the whole factor
     if (N.solve_ready && N.SP.panel_pool != N.gpanel) {
         N.SP.panel_pool = N.gpanel;  // gathered buffer allocated after the plan was built
+        N.SPM.panel_pool = N.gpanel;
         if (N.solve_gexec) (void)hipGraphExecDestroy(N.solve_gexec);
         if (N.solve_graph) (void)hipGraphDestroy(N.solve_graph);
+        if (N.solve_multi_gexec) (void)hipGraphExecDestroy(N.solve_multi_gexec);
+        if (N.solve_multi_graph) (void)hipGraphDestroy(N.solve_multi_graph);
         N.solve_gexec = nullptr;
         N.solve_graph = nullptr;
+        N.solve_multi_gexec = nullptr;
+        N.solve_multi_graph = nullptr;
     }
     if (!N.solve_ready) TRY(solve_build(N));
+    return SC_OK;
+}
+
+int64_t numeric_solve_device(Numeric& N, const double* d_b, double* d_x) {
+    if (!N.factored) return SC_ERR_STATE;
+    const int64_t st = numeric_status(N);
+    if (st != SC_OK) return st;
+    TRY(solve_prepare(N));
     const int64_t n = N.S->n;
     if (n == 0) return SC_OK;
     hipStream_t s0 = N.stream;
@@ -270,6 +283,100 @@ int64_t numeric_solve_host(Numeric& N, const double* b, double* x) {
     TRY(numeric_solve_device(N, N.d_sbuf, N.d_sbuf));
     HIP_TRY(hipMemcpy(x, N.d_sbuf, nb, hipMemcpyDeviceToHost));
     return SC_OK;
+}
+
+// ---------------- panel solves (SOLVE_RHS right-hand sides per sweep) ----------------
+// The 16-wide twins of the plan's work buffers, at the first multi solve only.
+static int64_t solve_multi_build(Numeric& N) {
+    const int64_t n1 = std::max<int64_t>(N.S->n, 1);
+    void* p = nullptr;
+    N.SPM = N.SP;
+    TRY(dalloc(N, (size_t)n1 * 3 * SOLVE_RHS * sizeof(double), p));
+    N.d_mbuf = (double*)p;
+    N.SPM.c = N.d_mbuf + n1 * SOLVE_RHS;
+    N.SPM.y = N.d_mbuf + 2 * n1 * SOLVE_RHS;
+    TRY(dalloc(N, (size_t)std::max<int64_t>(N.u_total, 1) * SOLVE_RHS * sizeof(double), p));
+    N.SPM.u = (double*)p;
+    TRY(dalloc(N, (size_t)N.solve_max_g * SOLVE_NB * SOLVE_RHS * sizeof(double), p));
+    N.SPM.part = (double*)p;
+    N.multi_ready = true;
+    return SC_OK;
+}
+
+// in / out: the copy kinds of the caller's B and X (device or host memory)
+static int64_t solve_multi(Numeric& N, int32_t nrhs, const double* B, int64_t ldb, double* X, int64_t ldx,
+                           hipMemcpyKind in, hipMemcpyKind out) {
+    if (!N.factored) return SC_ERR_STATE;
+    const int64_t st = numeric_status(N);
+    if (st != SC_OK) return st;
+    TRY(solve_prepare(N));
+    const int64_t n = N.S->n;
+    if (n == 0 || nrhs == 0) return SC_OK;
+    if (!N.multi_ready) TRY(solve_multi_build(N));
+    hipStream_t s0 = N.stream;
+    const SolvePlan& P = N.SPM;
+    // the graph solves the handle's own panel io = d_mbuf[0, 16 n) (column-major, the
+    // caller's order) in place, so it is captured once, whatever the caller passes
+    double* io = N.d_mbuf;
+    const size_t wide = (size_t)SOLVE_RHS * sizeof(double);
+    auto sweeps = [&]() -> hipError_t {
+        hipError_t e = launch_permute_multi(P.c, io, N.d_post, n, false, s0);
+        if (e == hipSuccess) e = hipMemsetAsync(P.u, 0, (size_t)std::max<int64_t>(N.u_total, 1) * wide, s0);
+        for (size_t i = 0; e == hipSuccess && i < N.solve_steps.size(); ++i) {
+            const Numeric::SolveStep& t = N.solve_steps[i];
+            e = launch_solve_fwd_gather_multi(P, N.d_sgather + t.gaoff, t.gacount, s0);
+            if (e == hipSuccess) e = launch_solve_fwd_multi(P, N.d_sfwd + t.foff, t.fcount, s0);
+        }
+        if (e == hipSuccess) e = hipMemcpyAsync(P.c, P.y, (size_t)n * wide, hipMemcpyDeviceToDevice, s0);
+        for (size_t i = N.solve_steps.size(); e == hipSuccess && i-- > 0;) {
+            const Numeric::SolveStep& t = N.solve_steps[i];
+            e = launch_solve_gemv_multi(P, N.d_sgemv + t.goff, t.gcount, s0);
+            if (e == hipSuccess) e = launch_solve_diag_multi(P, N.d_sdiag + t.doff, t.dcount, s0);
+        }
+        if (e == hipSuccess) e = launch_permute_multi(P.c, io, N.d_post, n, true, s0);
+        return e;
+    };
+    if (!N.solve_multi_gexec && !N.solve_eager) {  // a single-stream chain, like the single-vector graph
+        HIP_TRY(hipStreamBeginCapture(s0, hipStreamCaptureModeThreadLocal));
+        hipError_t e = sweeps();
+        hipGraph_t g = nullptr;
+        hipError_t e2 = hipStreamEndCapture(s0, &g);
+        HIP_TRY(e);
+        HIP_TRY(e2);
+        N.solve_multi_graph = g;
+        HIP_TRY(hipGraphInstantiate(&N.solve_multi_gexec, g, nullptr, nullptr, 0));
+    }
+    if (N.inv_gen != N.factor_gen) {  // shared with the single-vector solve
+        HIP_TRY(launch_solve_inv(N.SP, N.d_sinv, N.n_sinv, N.d_sinv2, N.n_sinv2, s0));
+        N.inv_gen = N.factor_gen;
+    }
+    const size_t colb = (size_t)n * sizeof(double);
+    for (int32_t j0 = 0; j0 < nrhs; j0 += SOLVE_RHS) {
+        const int nr = std::min<int32_t>(SOLVE_RHS, nrhs - j0);
+        HIP_TRY(hipMemcpy2DAsync(io, colb, B + (int64_t)j0 * ldb, (size_t)ldb * sizeof(double), colb, (size_t)nr, in,
+                                 s0));
+        // a partial panel: true zero columns, never the caller's memory
+        if (nr < SOLVE_RHS) HIP_TRY(hipMemsetAsync(io + (int64_t)nr * n, 0, (size_t)(SOLVE_RHS - nr) * colb, s0));
+        if (N.solve_eager)
+            HIP_TRY(sweeps());
+        else
+            HIP_TRY(hipGraphLaunch(N.solve_multi_gexec, s0));
+        HIP_TRY(hipMemcpy2DAsync(X + (int64_t)j0 * ldx, (size_t)ldx * sizeof(double), io, colb, colb, (size_t)nr, out,
+                                 s0));
+        // host memory: one panel staged at a time
+        if (out != hipMemcpyDeviceToDevice) HIP_TRY(hipStreamSynchronize(s0));
+    }
+    HIP_TRY(hipStreamSynchronize(s0));
+    return SC_OK;
+}
+
+int64_t numeric_solve_device_multi(Numeric& N, int32_t nrhs, const double* d_B, int64_t ldb, double* d_X,
+                                   int64_t ldx) {
+    return solve_multi(N, nrhs, d_B, ldb, d_X, ldx, hipMemcpyDeviceToDevice, hipMemcpyDeviceToDevice);
+}
+
+int64_t numeric_solve_host_multi(Numeric& N, int32_t nrhs, const double* B, int64_t ldb, double* X, int64_t ldx) {
+    return solve_multi(N, nrhs, B, ldb, X, ldx, hipMemcpyHostToDevice, hipMemcpyDeviceToHost);
 }
 
 }  // namespace sc
