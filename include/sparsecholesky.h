@@ -34,7 +34,7 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define SC_VERSION 121 /* still 1.2.1, additive: sc_solve_host_multi / sc_solve_device_multi (nrhs right-hand sides); 1.2.1:small merged fronts amalgamated past relax_wmax (different supernode partition of some inputs, same L); 1.2.0: persistent slab chain options removed; panel_prefactor, dist_local_pieces and SC_ORDER_AMD added; out-of-range lookahead / inner_order / ordering rejected */
+#define SC_VERSION 121 /* still 1.2.1, additive: the factor operators sc_apply_host / sc_apply_device / sc_apply_host_multi / sc_apply_device_multi (enum sc_factor_op) and sc_logdet; still 1.2.1, additive: sc_solve_host_multi / sc_solve_device_multi (nrhs right-hand sides); 1.2.1:small merged fronts amalgamated past relax_wmax (different supernode partition of some inputs, same L); 1.2.0: persistent slab chain options removed; panel_prefactor, dist_local_pieces and SC_ORDER_AMD added; out-of-range lookahead / inner_order / ordering rejected */
 
 enum sc_status {
     SC_OK = 0,
@@ -294,6 +294,50 @@ int64_t sc_solve_device_multi(sc_numeric* num, int32_t nrhs, const double* d_B, 
                               double* d_X, int64_t ldx);
 int64_t sc_solve_host_multi(sc_numeric* num, int32_t nrhs, const double* B, int64_t ldb,
                             double* X, int64_t ldx);
+
+/* Factor operators on the GPU (CHOLMOD's cholmod_solve systems L, Lt, P, Pt; the
+ * products and the log-determinant besides).  P A P^T = L L^T with L exactly the
+ * matrix sc_export_L returns, in the same numbering: the order of P A P^T, (P A P^T)[k,
+ * l] = A[perm[k], perm[l]] with perm = sc_symbolic_perm (the identity under
+ * SC_ORDER_NATURAL, where PERM and PERM_T are copies).  Hence A^-1 = P^T L^-T L^-1 P
+ * and A = P^T L L^T P; the etree postorder the kernels work in stays internal. */
+enum sc_factor_op {
+    SC_OP_SOLVE_A = 0,  /* X = A^-1 B   (what sc_solve_* compute) */
+    SC_OP_SOLVE_L = 1,  /* X = L^-1 B */
+    SC_OP_SOLVE_LT = 2, /* X = L^-T B */
+    SC_OP_MUL_L = 3,    /* X = L B */
+    SC_OP_MUL_LT = 4,   /* X = L^T B */
+    SC_OP_PERM = 5,     /* X = P B  : X[k] = B[perm[k]] */
+    SC_OP_PERM_T = 6    /* X = P^T B: X[perm[k]] = B[k] */
+};
+/* X = op(B).  The single-vector entry points take vectors of length n and run the
+ * single-vector kernels of sc_solve_host / sc_solve_device for the half solves; the
+ * _multi entry points take column-major B and X as sc_solve_*_multi do and run the
+ * 16-column panel kernels.  The products (SC_OP_MUL_L, SC_OP_MUL_LT) exist as panel
+ * kernels only: the single-vector entry points run them on a panel of one column, so a
+ * single-vector product equals column 0 of the _multi call bitwise.  SC_OP_SOLVE_A is
+ * the sc_solve_* path of the same family.  SC_OP_PERM, SC_OP_SOLVE_L, SC_OP_SOLVE_LT,
+ * SC_OP_PERM_T applied in this order give sc_solve_*'s result of the same family
+ * bitwise.  Every op: x may be b (X may be B when ldx == ldb); results are bitwise
+ * repeatable and a column does not depend on what travels with it.  The products never
+ * read the diagonal-block inverses the solves store after a factorization, and give the
+ * same bits before and after them.  Returns, argument checks, synchrony and the
+ * collective rule on multi-rank handles are those of sc_solve_device /
+ * sc_solve_device_multi (status > 0: nothing computed, X untouched; SC_ERR_STATE before
+ * a factorization; nrhs == 0 or n == 0: SC_OK); an op outside the enum: SC_ERR_ARG.
+ * Device memory: the solves' buffers (a product or a _multi call allocates the panel
+ * work buffers where sc_solve_*_multi has not yet) and one int32 per row when a
+ * fill-reducing ordering is in effect; nothing else. */
+int64_t sc_apply_device(sc_numeric* num, int32_t op, const double* d_b, double* d_x);
+int64_t sc_apply_host(sc_numeric* num, int32_t op, const double* b, double* x);
+int64_t sc_apply_device_multi(sc_numeric* num, int32_t op, int32_t nrhs, const double* d_B, int64_t ldb,
+                              double* d_X, int64_t ldx);
+int64_t sc_apply_host_multi(sc_numeric* num, int32_t op, int32_t nrhs, const double* B, int64_t ldb,
+                            double* X, int64_t ldx);
+/* log det A = 2 sum_j log L(j, j), from the panels' diagonals on the device, reduced in
+ * a fixed order: bitwise repeatable across calls and handles.  Status and collective
+ * rules of the solves (> 0: *logdet untouched). */
+int64_t sc_logdet(sc_numeric* num, double* logdet);
 
 /* ---------------- reference-API helpers (host) ----------------
  * Each mirrors one reference function, with int64 column pointers. */

@@ -45,12 +45,15 @@ __all__ = [
     "etree", "post_order", "col_count", "ereach", "schol", "chol", "chol_sn",
     "csc_to_dense", "compute_levels", "compute_supernodes", "atree", "laplacian3d",
     "Symbolic", "Numeric", "Options",
+    "SC_OP_SOLVE_A", "SC_OP_SOLVE_L", "SC_OP_SOLVE_LT", "SC_OP_MUL_L", "SC_OP_MUL_LT", "SC_OP_PERM", "SC_OP_PERM_T",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libsparsecholesky_amd.so")
 
 SC_OK = 0
+# enum sc_factor_op: what Numeric.apply / sc_apply_* compute from the factor P A P^T = L L^T
+SC_OP_SOLVE_A, SC_OP_SOLVE_L, SC_OP_SOLVE_LT, SC_OP_MUL_L, SC_OP_MUL_LT, SC_OP_PERM, SC_OP_PERM_T = range(7)
 _STATUS = {
     -1: "invalid argument", -2: "host allocation failed", -3: "HIP runtime error",
     -4: "device allocation failed", -5: "call out of order", -6: "communication error",
@@ -130,6 +133,11 @@ _SIGS = [
     ("sc_solve_device", _I64, [_P, _P, _P]),
     ("sc_solve_device_multi", _I64, [_P, _I32, _P, _I64, _P, _I64]),
     ("sc_solve_host_multi", _I64, [_P, _I32, _P, _I64, _P, _I64]),
+    ("sc_apply_device", _I64, [_P, _I32, _P, _P]),
+    ("sc_apply_host", _I64, [_P, _I32, _P, _P]),
+    ("sc_apply_device_multi", _I64, [_P, _I32, _I32, _P, _I64, _P, _I64]),
+    ("sc_apply_host_multi", _I64, [_P, _I32, _I32, _P, _I64, _P, _I64]),
+    ("sc_logdet", _I64, [_P, _P]),
     ("sc_etree", _I64, [_I64, _P, _P, _P]),
     ("sc_post_order", _I64, [_I64, _P, _P]),
     ("sc_col_count", _I64, [_I64, _P, _P, _P, _P, _P]),
@@ -742,6 +750,78 @@ class Numeric:
         if st > 0:
             raise LibraryError(f"solve_device_multi: A is not positive definite (column {st})")
         return st
+
+    def apply(self, b: np.ndarray, op: int) -> np.ndarray:
+        """op(b) with the factor P A P^T = L L^T on the GPU (host arrays in / out); op is one
+        of the SC_OP_* constants, L the matrix :meth:`export` returns, in its numbering.  b of
+        shape (n,): the single-vector entry point (sc_apply_host); b of shape (n, k): the
+        16-column panel family (sc_apply_host_multi), returned as (n, k)."""
+        if np.ndim(b) == 2:
+            B = np.asfortranarray(b, dtype=np.float64)
+            n, k = B.shape
+            if n != self.symb.n:
+                raise ValueError(f"apply: b has {n} rows, the matrix {self.symb.n}")
+            X = np.zeros((n, k), dtype=np.float64, order="F")
+            ld = max(n, 1)
+            st = _check(lib().sc_apply_host_multi(self.h, int(op), k, _ptr(B), ld, _ptr(X), ld), "apply")
+            if st > 0:
+                raise LibraryError(f"apply: A is not positive definite (column {st})")
+            return X
+        b = np.ascontiguousarray(b, dtype=np.float64)
+        if b.shape[0] != self.symb.n:
+            raise ValueError(f"apply: b has {b.shape[0]} rows, the matrix {self.symb.n}")
+        x = np.zeros_like(b)
+        st = _check(lib().sc_apply_host(self.h, int(op), _ptr(b), _ptr(x)), "apply")
+        if st > 0:
+            raise LibraryError(f"apply: A is not positive definite (column {st})")
+        return x
+
+    def solve_L(self, b: np.ndarray) -> np.ndarray:
+        """L^-1 b."""
+        return self.apply(b, SC_OP_SOLVE_L)
+
+    def solve_Lt(self, b: np.ndarray) -> np.ndarray:
+        """L^-T b."""
+        return self.apply(b, SC_OP_SOLVE_LT)
+
+    def mul_L(self, z: np.ndarray) -> np.ndarray:
+        """L z."""
+        return self.apply(z, SC_OP_MUL_L)
+
+    def mul_Lt(self, z: np.ndarray) -> np.ndarray:
+        """L^T z."""
+        return self.apply(z, SC_OP_MUL_LT)
+
+    def apply_P(self, b: np.ndarray) -> np.ndarray:
+        """P b: x[k] = b[perm[k]] with perm = :meth:`Symbolic.perm`."""
+        return self.apply(b, SC_OP_PERM)
+
+    def apply_Pt(self, b: np.ndarray) -> np.ndarray:
+        """P^T b: x[perm[k]] = b[k]."""
+        return self.apply(b, SC_OP_PERM_T)
+
+    def apply_device(self, op: int, d_b_ptr: int, d_x_ptr: int) -> int:
+        """x = op(b) with device vectors (may alias)."""
+        st = _check(lib().sc_apply_device(self.h, int(op), C.c_void_p(d_b_ptr), C.c_void_p(d_x_ptr)), "apply_device")
+        if st > 0:
+            raise LibraryError(f"apply_device: A is not positive definite (column {st})")
+        return st
+
+    def apply_device_multi(self, op: int, d_B_ptr: int, nrhs: int, ldb: int, d_X_ptr: int, ldx: int) -> int:
+        """X = op(B) with device arrays, column-major as for :meth:`solve_device_multi`."""
+        st = _check(lib().sc_apply_device_multi(self.h, int(op), nrhs, C.c_void_p(d_B_ptr), ldb, C.c_void_p(d_X_ptr),
+                                                ldx), "apply_device_multi")
+        if st > 0:
+            raise LibraryError(f"apply_device_multi: A is not positive definite (column {st})")
+        return st
+
+    def logdet(self) -> float:
+        """log det A = 2 sum_j log L(j, j), reduced on the GPU in a fixed order."""
+        v = C.c_double()
+        st = _check(lib().sc_logdet(self.h, C.byref(v)), "logdet")
+        if st > 0:
+            raise LibraryError(f"logdet: A is not positive definite (column {st})")
+        return v.value
 
     def __del__(self):
         h = getattr(self, "h", None)

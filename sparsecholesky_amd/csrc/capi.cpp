@@ -438,6 +438,67 @@ int64_t sc_solve_device_multi(sc_numeric* num, int32_t nrhs, const double* d_B, 
     return rc;
 }
 
+// ---- factor operators ----
+static int64_t apply_op_arg(int32_t op, const char* what) {
+    if (op >= SC_OP_SOLVE_A && op <= SC_OP_PERM_T) return SC_OK;
+    g_last_error = std::string(what) + ": op is not an sc_factor_op";
+    return SC_ERR_ARG;
+}
+
+static int64_t apply_vec_args(sc_numeric* num, int32_t op, const double* b, double* x, const char* what) {
+    if (!num || !num->N || !b || !x) {
+        g_last_error = std::string(what) + ((!num || !num->N) ? ": null handle" : ": null b or x");
+        return SC_ERR_ARG;
+    }
+    return apply_op_arg(op, what);
+}
+
+int64_t sc_apply_device(sc_numeric* num, int32_t op, const double* d_b, double* d_x) {
+    int64_t rc = apply_vec_args(num, op, d_b, d_x, "sc_apply_device");
+    if (rc != SC_OK) return rc;
+    rc = sc::numeric_apply_device(*num->N, op, d_b, d_x);
+    if (rc < 0) g_last_error = num->N->err;
+    return rc;
+}
+
+int64_t sc_apply_host(sc_numeric* num, int32_t op, const double* b, double* x) {
+    int64_t rc = apply_vec_args(num, op, b, x, "sc_apply_host");
+    if (rc != SC_OK) return rc;
+    rc = sc::numeric_apply_host(*num->N, op, b, x);
+    if (rc < 0) g_last_error = num->N->err;
+    return rc;
+}
+
+int64_t sc_apply_device_multi(sc_numeric* num, int32_t op, int32_t nrhs, const double* d_B, int64_t ldb, double* d_X,
+                              int64_t ldx) {
+    int64_t rc = solve_multi_args(num, nrhs, d_B, ldb, d_X, ldx, "sc_apply_device_multi");
+    if (rc == SC_OK) rc = apply_op_arg(op, "sc_apply_device_multi");
+    if (rc != SC_OK) return rc;
+    rc = sc::numeric_apply_device_multi(*num->N, op, nrhs, d_B, ldb, d_X, ldx);
+    if (rc < 0) g_last_error = num->N->err;
+    return rc;
+}
+
+int64_t sc_apply_host_multi(sc_numeric* num, int32_t op, int32_t nrhs, const double* B, int64_t ldb, double* X,
+                            int64_t ldx) {
+    int64_t rc = solve_multi_args(num, nrhs, B, ldb, X, ldx, "sc_apply_host_multi");
+    if (rc == SC_OK) rc = apply_op_arg(op, "sc_apply_host_multi");
+    if (rc != SC_OK) return rc;
+    rc = sc::numeric_apply_host_multi(*num->N, op, nrhs, B, ldb, X, ldx);
+    if (rc < 0) g_last_error = num->N->err;
+    return rc;
+}
+
+int64_t sc_logdet(sc_numeric* num, double* logdet) {
+    if (!num || !num->N || !logdet) {
+        g_last_error = (!num || !num->N) ? "sc_logdet: null handle" : "sc_logdet: null logdet";
+        return SC_ERR_ARG;
+    }
+    const int64_t rc = sc::numeric_logdet(*num->N, logdet);
+    if (rc < 0) g_last_error = num->N->err;
+    return rc;
+}
+
 // ---- reference-API helpers ----
 int64_t sc_etree(int64_t n, const int64_t* Ap, const int32_t* Ai, int32_t* parent) {
     if (n < 0 || !Ap || !parent) return SC_ERR_ARG;

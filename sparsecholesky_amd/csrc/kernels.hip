@@ -2347,7 +2347,10 @@ struct DiagA {
 };
 __device__ __forceinline__ int wave_id() { return __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); }
 
-template <bool TRANS>
+// INV = false: the factor's own block instead of its inverse, L(i, k), k <= i, at (row i,
+// column k) with the diagonal as it is: only the lower triangle is read, never the
+// stored inverses above it.
+template <bool TRANS, bool INV = true>
 __device__ __forceinline__ void diag_load_multi(const double* __restrict__ blk, int m, int nb, DiagA& A) {
     const int lane = threadIdx.x & 63, wv = wave_id();
     const int il = lane & 15, kq = lane >> 4;
@@ -2360,16 +2363,18 @@ __device__ __forceinline__ void diag_load_multi(const double* __restrict__ blk, 
         const int gi = 16 * I + il, gk = 4 * ks + kq;
         // X128(gi, gk) (TRANS: X128(gk, gi)) = block entry (row = the smaller, column = the larger index)
         const int hi = TRANS ? gk : gi, lw = TRANS ? gi : gk;
-        A.a[q] = buf_ld(rs, ((hi < nb) & (lw <= hi)) ? (hi * m + lw) * 8 : BUF_DEAD, 0);
+        A.a[q] = buf_ld(rs, ((hi < nb) & (lw <= hi)) ? (INV ? hi * m + lw : lw * m + hi) * 8 : BUF_DEAD, 0);
     }
+    if constexpr (INV) {
 #pragma unroll
-    for (int e = 0; e < 2; ++e) {
-        const int gi = 16 * (e ? Il : Is) + il;
-        A.d[e] = buf_ld(rs, gi < nb ? (gi * m + gi) * 8 : BUF_DEAD, 0);
+        for (int e = 0; e < 2; ++e) {
+            const int gi = 16 * (e ? Il : Is) + il;
+            A.d[e] = buf_ld(rs, gi < nb ? (gi * m + gi) * 8 : BUF_DEAD, 0);
+        }
     }
 }
 
-template <bool TRANS>
+template <bool TRANS, bool INV = true>
 __device__ __forceinline__ void diag_mfma_multi(const DiagA& A, int nb, const double* Cs, double* Ys) {
     const int lane = threadIdx.x & 63, wv = wave_id();
     const int il = lane & 15, kq = lane >> 4;
@@ -2380,7 +2385,7 @@ __device__ __forceinline__ void diag_mfma_multi(const DiagA& A, int nb, const do
         const int I = e ? Il : Is;
         if (16 * I >= nb) continue;  // wave-uniform: the tile's rows are all past nb
         const int gi = 16 * I + il;
-        const double dinv = gi < nb ? 1.0 / A.d[e] : 0.0;  // dead: 0, not 1/0
+        const double dinv = (INV && gi < nb) ? 1.0 / A.d[e] : 0.0;  // dead: 0, not 1/0
 #pragma unroll
         for (int g = 0; g < (e ? DIAG_SLOTS - DIAG_SHORT : DIAG_SHORT) / 4; ++g) {
             const int ks0 = (e ? 0 : (TRANS ? 16 : 0)) + 4 * g;
@@ -2388,7 +2393,7 @@ __device__ __forceinline__ void diag_mfma_multi(const DiagA& A, int nb, const do
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 const int gk = 4 * (ks0 + u) + kq;
-                const double av = gi == gk ? dinv : A.a[(e ? DIAG_SHORT : 0) + 4 * g + u];
+                const double av = (INV && gi == gk) ? dinv : A.a[(e ? DIAG_SHORT : 0) + 4 * g + u];
                 acc[e] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, Cs[gk * SOLVE_RHS + il], acc[e], 0, 0, 0);
             }
         }
@@ -2688,6 +2693,305 @@ __global__ __launch_bounds__(256) void permute_multi_kernel(double* __restrict__
 #pragma unroll
         for (int q = 0; q < 4; ++q) io[p + (jq + 4 * q) * n] = tile[il][jq + 4 * q];
     }
+}
+
+// ---------------------------------------------------------------------------
+// Products with the factor, X = L Z and X = L^T Z, in the panel family: the transposes
+// of the two sweeps above, on the same task lists and buffers.  The input Z sits in P.y
+// (read-only), the result is built in P.c.  A diagonal block is read through its lower
+// triangle only (entries (i, k), k <= i, the diagonal as stored): the strict upper
+// triangles hold the stored inverses once a solve has run, and a product neither needs
+// them nor depends on whether they are there.  No atomics, every sum in a fixed order,
+// and a column of X depends on its own column of Z only.
+// ---------------------------------------------------------------------------
+// X = L Z, one step of the bottom-up sweep: tasks as solve_fwd_kernel.  Wave v forms
+// ACC(64 x 16) = L(rows, blk) Z_blk for rows r0 + 64 v .. and adds it to c (rows < w:
+// the front's own later pivots) or to the front's u (its contribution-block rows, which
+// the parent's gather adds in child order); the writer also adds L_blk Z_blk (lower
+// triangular) to c_blk.  c and u start at zero.
+__global__ __launch_bounds__(SOLVE_ROWS) void mul_l_multi_kernel(SolvePlan P, const int4* __restrict__ tasks) {
+    __shared__ double Zs[SOLVE_PANEL], Ys[SOLVE_PANEL];
+    const int4 t = tasks[blockIdx.x];
+    const int s = t.x, k0 = t.y, r0 = t.z;
+    const int tid = threadIdx.x, lane = tid & 63, wv = wave_id();
+    const int il = lane & 15, kq = lane >> 4;
+    const int c0 = P.sn_start[s];
+    const int w = P.sn_start[s + 1] - c0;
+    const int m = P.sn_m[s];
+    const int nb = min(SOLVE_NB, w - k0);
+    const double* __restrict__ pan = P.panel_pool + P.panel_off[s] + (int64_t)k0 * m;
+    DiagA la;
+    if (t.w) diag_load_multi<false, false>(pan + k0, m, nb, la);  // the writer's L_blk
+    // the whole offset in the VGPR: the range check masks rows >= m and columns >= nb
+    const __amdgpu_buffer_rsrc_t rs = buf_rsrc(pan, (uint32_t)((int64_t)nb * m * 8));
+    const int rb = r0 + 64 * wv;  // this wave's rows
+    double a[2][4][PNB / 4];
+    auto load_half = [&](int h) {
+#pragma unroll
+        for (int ti = 0; ti < 4; ++ti)
+#pragma unroll
+            for (int ks = 0; ks < PNB / 4; ++ks) {
+                const int r = rb + 16 * ti + il, col = h * PNB + 4 * ks + kq;
+                a[h][ti][ks] = buf_ld(rs, ((r0 >= 0) & (r < m) & (col < nb)) ? (col * m + r) * 8 : BUF_DEAD, 0);
+            }
+    };
+    load_half(0);
+    const double* zblk = P.y + (int64_t)(c0 + k0) * SOLVE_RHS;
+#pragma unroll
+    for (int q = 0; q < SOLVE_PANEL / SOLVE_ROWS; ++q) {
+        const int e = tid + SOLVE_ROWS * q;
+        Zs[e] = (e >> 4) < nb ? zblk[e] : 0.0;
+    }
+    __syncthreads();
+    if (t.w) {  // workgroup-uniform
+        diag_mfma_multi<false, false>(la, nb, Zs, Ys);
+        __syncthreads();
+        // the block's rows of c: earlier steps of the front and the gather have added to
+        // them in earlier launches, no other workgroup of this step does
+        double* __restrict__ cblk = P.c + (int64_t)(c0 + k0) * SOLVE_RHS;
+#pragma unroll
+        for (int q = 0; q < SOLVE_PANEL / SOLVE_ROWS; ++q) {
+            const int e = tid + SOLVE_ROWS * q;
+            if ((e >> 4) < nb) cblk[e] += Ys[e];
+        }
+    }
+    if (r0 < 0) return;
+    if (nb > PNB) load_half(1);  // in flight under the first half's products
+    double4_t acc[4];
+#pragma unroll
+    for (int ti = 0; ti < 4; ++ti) acc[ti] = double4_t {0.0, 0.0, 0.0, 0.0};
+    // tiles past m and 16-column groups past nb are skipped (wave-uniform; their A is all zeros)
+    auto mfma_half = [&](int h) {
+        double bv[PNB / 4];
+#pragma unroll
+        for (int ks = 0; ks < PNB / 4; ++ks) bv[ks] = Zs[(h * PNB + 4 * ks + kq) * SOLVE_RHS + il];
+#pragma unroll
+        for (int ti = 0; ti < 4; ++ti) {
+            if (rb + 16 * ti >= m) continue;
+#pragma unroll
+            for (int g = 0; g < PNB / 16; ++g) {
+                if (h * PNB + 16 * g >= nb) continue;
+#pragma unroll
+                for (int u = 0; u < 4; ++u)
+                    acc[ti] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[h][ti][4 * g + u], bv[4 * g + u], acc[ti], 0, 0, 0);
+            }
+        }
+    };
+    mfma_half(0);
+    if (nb > PNB) mfma_half(1);
+    // one writer per row and step, as in solve_fwd_multi_kernel; 16 lanes write one 128-byte row
+    const int32_t* __restrict__ rows = P.rows + P.rows_ptr[s];
+    double* __restrict__ us = P.u + P.u_off[s] * SOLVE_RHS;
+#pragma unroll
+    for (int ti = 0; ti < 4; ++ti)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const int r = rb + 16 * ti + kq + 4 * g;
+            if (r < m) {
+                double* dst = r < w ? P.c + (int64_t)rows[r] * SOLVE_RHS : us + (int64_t)(r - w) * SOLVE_RHS;
+                dst[il] += acc[ti][g];
+            }
+        }
+}
+
+// X = L^T Z, part 1: workgroup (s, k0, r0) leaves its partial P(128 x 16) = L(rows,
+// blk)^T Z(rows) in part[task]: solve_gemv_multi_kernel with Z read from P.y and the
+// opposite sign (L transposed through LDS one 64-column half at a time, wave v owning
+// rows r0 + 64 v .., the four waves' results summed in wave order).
+__global__ __launch_bounds__(SOLVE_ROWS) void mul_lt_gemv_multi_kernel(SolvePlan P, const int4* __restrict__ tasks) {
+    __shared__ double T[SOLVE_ROWS / 64][PNB][GEMV_LD];  // T[v][j][row] = L(r0 + 64 v + row, j)
+    const int4 t = tasks[blockIdx.x];
+    const int s = t.x, k0 = t.y, r0 = t.z;
+    const int tid = threadIdx.x, lane = tid & 63, wv = wave_id();
+    const int il = lane & 15, kq = lane >> 4;
+    const int c0 = P.sn_start[s];
+    const int w = P.sn_start[s + 1] - c0;
+    const int m = P.sn_m[s];
+    const int nb = min(SOLVE_NB, w - k0);
+    const double* __restrict__ pan = P.panel_pool + P.panel_off[s] + (int64_t)k0 * m;
+    const int32_t* __restrict__ rows = P.rows + P.rows_ptr[s];
+    const int r = r0 + tid;
+    const bool live = r < m;
+    double bz[16];  // Z(r0 + 64 v + 4 ks + kq, il); dead rows 0
+#pragma unroll
+    for (int ks = 0; ks < 16; ++ks) {
+        const int rr = r0 + 64 * wv + 4 * ks + kq;
+        bz[ks] = rr < m ? P.y[(int64_t)rows[rr] * SOLVE_RHS + il] : 0.0;
+    }
+    const __amdgpu_buffer_rsrc_t rs = buf_rsrc(pan, (uint32_t)((int64_t)nb * m * 8));
+    double v[2][PNB];  // both halves' loads go out at once (the second waits in registers)
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int q = 0; q < PNB; ++q) {
+            const int col = h * PNB + q;
+            v[h][q] = buf_ld(rs, (live & (col < nb)) ? (col * m + r) * 8 : BUF_DEAD, 0);
+        }
+    // R[v][j][16]: wave v's result, over the start of its own T[v] once its products are done
+    constexpr int W = PNB * GEMV_LD;
+    double* R = &T[0][0][0];
+    auto half = [&](int h) {
+#pragma unroll
+        for (int q = 0; q < PNB; ++q) T[wv][q][lane] = v[h][q];
+        __syncthreads();
+        double4_t acc[4];
+#pragma unroll
+        for (int I = 0; I < 4; ++I) acc[I] = double4_t {0.0, 0.0, 0.0, 0.0};
+        // tiles past nb and 16-row groups past m are skipped (wave-uniform; zeros)
+#pragma unroll
+        for (int I = 0; I < 4; ++I) {
+            if (h * PNB + 16 * I >= nb) continue;
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                if (r0 + 64 * wv + 16 * g >= m) continue;
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const int ks = 4 * g + u;
+                    acc[I] = __builtin_amdgcn_mfma_f64_16x16x4f64(T[wv][16 * I + il][4 * ks + kq], bz[ks], acc[I], 0, 0,
+                                                                  0);
+                }
+            }
+        }
+#pragma unroll
+        for (int I = 0; I < 4; ++I)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) R[wv * W + (16 * I + kq + 4 * g) * SOLVE_RHS + il] = acc[I][g];
+        __syncthreads();
+        double* __restrict__ out = P.part + ((int64_t)blockIdx.x * SOLVE_NB + h * PNB) * SOLVE_RHS;
+#pragma unroll
+        for (int q = 0; q < PNB * SOLVE_RHS / SOLVE_ROWS; ++q) {
+            const int e = tid + SOLVE_ROWS * q;
+            out[e] = R[e] + R[W + e] + R[2 * W + e] + R[3 * W + e];  // in wave order
+        }
+    };
+    half(0);
+    if (nb > PNB) {
+        __syncthreads();  // the first half's R fully read
+        half(1);
+    }
+}
+
+// X = L^T Z, part 2: X_blk = L_blk^T Z_blk plus the block's partials in task order, into
+// c.  No front waits for another: every row of c has this one writer.
+__global__ __launch_bounds__(256) void mul_lt_diag_multi_kernel(SolvePlan P, const int4* __restrict__ tasks) {
+    __shared__ double Zs[SOLVE_PANEL], Ys[SOLVE_PANEL];
+    const int4 t = tasks[blockIdx.x];
+    const int s = t.x, k0 = t.y;
+    const int tid = threadIdx.x;
+    const int c0 = P.sn_start[s];
+    const int w = P.sn_start[s + 1] - c0;
+    const int m = P.sn_m[s];
+    const int nb = min(SOLVE_NB, w - k0);
+    const double* __restrict__ blk = P.panel_pool + P.panel_off[s] + (int64_t)k0 * m + k0;
+    const double* __restrict__ zblk = P.y + (int64_t)(c0 + k0) * SOLVE_RHS;
+    double* __restrict__ cblk = P.c + (int64_t)(c0 + k0) * SOLVE_RHS;
+    DiagA la;
+    diag_load_multi<true, false>(blk, m, nb, la);
+    constexpr int NQ = SOLVE_PANEL / 256, DIAG_PF = 8;
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+        const int e = tid + 256 * q;
+        Zs[e] = (e >> 4) < nb ? zblk[e] : 0.0;
+    }
+    __syncthreads();
+    diag_mfma_multi<true, false>(la, nb, Zs, Ys);
+    __syncthreads();
+    // the partials in task order, DIAG_PF tasks in flight at a time (dead parts of a
+    // partial are never read)
+    double v[NQ];
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) v[q] = Ys[tid + 256 * q];
+    const double* __restrict__ part = P.part + (int64_t)t.z * SOLVE_PANEL;
+    for (int g0 = 0; g0 < t.w; g0 += DIAG_PF) {
+        double pv[DIAG_PF][NQ];
+#pragma unroll
+        for (int u = 0; u < DIAG_PF; ++u)
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) {
+                const int e = tid + 256 * q;
+                pv[u][q] = (g0 + u < t.w && (e >> 4) < nb) ? part[(int64_t)(g0 + u) * SOLVE_PANEL + e] : 0.0;
+            }
+#pragma unroll
+        for (int u = 0; u < DIAG_PF; ++u)
+            if (g0 + u < t.w) {
+#pragma unroll
+                for (int q = 0; q < NQ; ++q) v[q] += pv[u][q];
+            }
+    }
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+        const int e = tid + 256 * q;
+        if ((e >> 4) < nb) cblk[e] = v[q];
+    }
+}
+
+// log det A = 2 sum_j log L(j, j): the n diagonal entries straight from the panels
+// (internal column j of supernode s at panel_off[s] + (j - sn_start[s]) (m + 1); the
+// stored inverses never touch the diagonal), LOGDET_NT per workgroup, summed by a fixed
+// tree into part[workgroup]; then one workgroup sums the partials in index order.
+__device__ __forceinline__ double logdet_tree(double v, double* red) {
+    const int tid = threadIdx.x;
+    red[tid] = v;
+    __syncthreads();
+    for (int h = LOGDET_NT / 2; h > 0; h >>= 1) {
+        if (tid < h) red[tid] += red[tid + h];
+        __syncthreads();
+    }
+    return red[0];
+}
+
+__global__ __launch_bounds__(LOGDET_NT) void logdet_partial_kernel(SolvePlan P, int ns, int n,
+                                                                   double* __restrict__ part) {
+    __shared__ double red[LOGDET_NT];
+    const int j = (int)blockIdx.x * LOGDET_NT + (int)threadIdx.x;
+    double v = 0.0;
+    if (j < n) {
+        int lo = 0, hi = ns;  // sn_start[lo] <= j < sn_start[hi]
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (P.sn_start[mid] <= j)
+                lo = mid;
+            else
+                hi = mid;
+        }
+        v = log(P.panel_pool[P.panel_off[lo] + (int64_t)(j - P.sn_start[lo]) * (P.sn_m[lo] + 1)]);
+    }
+    const double sum = logdet_tree(v, red);
+    if (threadIdx.x == 0) part[blockIdx.x] = sum;
+}
+
+__global__ __launch_bounds__(LOGDET_NT) void logdet_final_kernel(const double* __restrict__ part, int np,
+                                                                 double* __restrict__ out) {
+    __shared__ double red[LOGDET_NT];
+    double v = 0.0;
+    for (int i = threadIdx.x; i < np; i += LOGDET_NT) v += part[i];
+    const double sum = logdet_tree(v, red);
+    if (threadIdx.x == 0) out[0] = 2.0 * sum;
+}
+
+hipError_t launch_mul_l_multi(const SolvePlan& P, const int4* tasks, int count, hipStream_t st) {
+    if (count <= 0) return hipSuccess;
+    hipLaunchKernelGGL(mul_l_multi_kernel, dim3(count), dim3(SOLVE_ROWS), 0, st, P, tasks);
+    return hipGetLastError();
+}
+
+hipError_t launch_mul_lt_gemv_multi(const SolvePlan& P, const int4* tasks, int count, hipStream_t st) {
+    if (count <= 0) return hipSuccess;
+    hipLaunchKernelGGL(mul_lt_gemv_multi_kernel, dim3(count), dim3(SOLVE_ROWS), 0, st, P, tasks);
+    return hipGetLastError();
+}
+
+hipError_t launch_mul_lt_diag_multi(const SolvePlan& P, const int4* tasks, int count, hipStream_t st) {
+    if (count <= 0) return hipSuccess;
+    hipLaunchKernelGGL(mul_lt_diag_multi_kernel, dim3(count), dim3(256), 0, st, P, tasks);
+    return hipGetLastError();
+}
+
+hipError_t launch_logdet(const SolvePlan& P, int ns, int64_t n, double* part, double* out, hipStream_t st) {
+    const int np = (int)((n + LOGDET_NT - 1) / LOGDET_NT);
+    if (np > 0) hipLaunchKernelGGL(logdet_partial_kernel, dim3(np), dim3(LOGDET_NT), 0, st, P, ns, (int)n, part);
+    hipLaunchKernelGGL(logdet_final_kernel, dim3(1), dim3(LOGDET_NT), 0, st, part, np, out);
+    return hipGetLastError();
 }
 
 hipError_t launch_solve_fwd_multi(const SolvePlan& P, const int4* tasks, int count, hipStream_t st) {

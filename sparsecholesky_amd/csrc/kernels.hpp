@@ -171,6 +171,23 @@ hipError_t launch_solve_diag_multi(const SolvePlan& P, const int4* tasks, int co
 hipError_t launch_permute_multi(double* c, double* io, const int32_t* perm, int64_t n, bool scatter,
                                 hipStream_t st);
 
+// Products with the factor in the panel family (fp64 MFMA), on the solves' task lists:
+// the input Z in P.y (read-only), the result in P.c.  Diagonal blocks are read through
+// their lower triangle only, so the stored inverses (launch_solve_inv) are never seen.
+// X = L Z: a bottom-up sweep, c and u zeroed first; per level launch_solve_fwd_gather_multi
+// (children's u into c / u), then per step tasks (s, k0, r0, writer) add L(rows, blk) Z_blk
+// into c (own later pivots) or u (contribution-block rows), the writer also L_blk Z_blk.
+hipError_t launch_mul_l_multi(const SolvePlan& P, const int4* tasks, int count, hipStream_t st);
+// X = L^T Z: tasks (s, k0, r0) leave L(rows, blk)^T Z(rows) in part, then tasks (s, k0, g0,
+// ng) write X_blk = L_blk^T Z_blk + the ng partials in order.  Steps are independent of
+// each other but for the part buffer they share.
+hipError_t launch_mul_lt_gemv_multi(const SolvePlan& P, const int4* tasks, int count, hipStream_t st);
+hipError_t launch_mul_lt_diag_multi(const SolvePlan& P, const int4* tasks, int count, hipStream_t st);
+// out[0] = 2 sum_j log L(j, j) over the n panel diagonals (ns supernodes), in a fixed
+// order: part[ceil(n / LOGDET_NT)] per-workgroup sums, then one workgroup over part.
+constexpr int LOGDET_NT = 256;
+hipError_t launch_logdet(const SolvePlan& P, int ns, int64_t n, double* part, double* out, hipStream_t st);
+
 // Small fronts (m <= maxm <= 128): one workgroup per front, factored in registers
 // (4 x 4 tiles per thread); seq: one workgroup runs the fronts in order (a whole
 // small tree in postorder, CBs through HBM).

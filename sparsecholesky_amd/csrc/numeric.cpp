@@ -632,10 +632,7 @@ void numeric_free(Numeric* Np) {
     (void)hipSetDevice(N.device);
     if (N.stream) (void)hipStreamSynchronize(N.stream);
     comm_destroy(N);
-    if (N.solve_gexec) (void)hipGraphExecDestroy(N.solve_gexec);
-    if (N.solve_graph) (void)hipGraphDestroy(N.solve_graph);
-    if (N.solve_multi_gexec) (void)hipGraphExecDestroy(N.solve_multi_gexec);
-    if (N.solve_multi_graph) (void)hipGraphDestroy(N.solve_multi_graph);
+    numeric_drop_solve_graphs(N);
     if (N.gexec) (void)hipGraphExecDestroy(N.gexec);
     if (N.graph) (void)hipGraphDestroy(N.graph);
     for (auto e : N.ev)

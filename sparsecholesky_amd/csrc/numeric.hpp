@@ -350,6 +350,13 @@ struct Numeric {
     double* d_mbuf = nullptr;          // io (n x SOLVE_RHS column-major), c, y (SOLVE_RHS-wide rows)
     hipGraph_t solve_multi_graph = nullptr;
     hipGraphExec_t solve_multi_gexec = nullptr;
+    // factor operators (numeric_apply_*): the etree postorder alone (d_post itself when no
+    // fill-reducing permutation is in effect), uploaded at the first apply, and one lazily
+    // captured graph per family (0 single vector, 1 panel) and op (sc_factor_op)
+    static constexpr int APPLY_OPS = 7;
+    int32_t* d_etpost = nullptr;
+    hipGraph_t apply_graph[2][APPLY_OPS] = {};
+    hipGraphExec_t apply_gexec[2][APPLY_OPS] = {};
 
     std::string err;
 };
@@ -398,6 +405,21 @@ int64_t numeric_solve_host(Numeric& N, const double* b, double* x);
 int64_t numeric_solve_device_multi(Numeric& N, int32_t nrhs, const double* d_B, int64_t ldb, double* d_X,
                                    int64_t ldx);
 int64_t numeric_solve_host_multi(Numeric& N, int32_t nrhs, const double* B, int64_t ldb, double* X, int64_t ldx);
+// Factor operators (op: sc_factor_op; L in the numbering of numeric_export, the order of
+// P A P^T): X = op(B).  The single-vector entry points run the single-vector kernels for
+// the half solves; the products have panel kernels only, so a single vector travels as a
+// panel of one column.  SC_OP_SOLVE_A is numeric_solve_*.  Buffers, status, ordering and
+// collective rules of the solves; x may be b.
+int64_t numeric_apply_device(Numeric& N, int32_t op, const double* d_b, double* d_x);
+int64_t numeric_apply_host(Numeric& N, int32_t op, const double* b, double* x);
+int64_t numeric_apply_device_multi(Numeric& N, int32_t op, int32_t nrhs, const double* d_B, int64_t ldb, double* d_X,
+                                   int64_t ldx);
+int64_t numeric_apply_host_multi(Numeric& N, int32_t op, int32_t nrhs, const double* B, int64_t ldb, double* X,
+                                 int64_t ldx);
+// log det A = 2 sum_j log L(j, j), reduced on the device in a fixed order.
+int64_t numeric_logdet(Numeric& N, double* logdet);
+// Destroys the captured solve and apply graphs (they point at one panel pool).
+void numeric_drop_solve_graphs(Numeric& N);
 int64_t debug_syrk(double* dC, int ldc, const double* dA, int lda, int M, int N, int K);
 int64_t numeric_chain_stamps(Numeric& N, int enable, uint64_t* out, int64_t cap);
 int64_t debug_bench(int which, int M, int K, int reps, int arg, double* tflops);

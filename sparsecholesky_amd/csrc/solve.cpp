@@ -193,6 +193,19 @@ static int64_t solve_build(Numeric& N) {
     return SC_OK;
 }
 
+void numeric_drop_solve_graphs(Numeric& N) {
+    auto drop = [](hipGraph_t& g, hipGraphExec_t& x) {
+        if (x) (void)hipGraphExecDestroy(x);
+        if (g) (void)hipGraphDestroy(g);
+        x = nullptr;
+        g = nullptr;
+    };
+    drop(N.solve_graph, N.solve_gexec);
+    drop(N.solve_multi_graph, N.solve_multi_gexec);
+    for (int f = 0; f < 2; ++f)
+        for (int op = 0; op < Numeric::APPLY_OPS; ++op) drop(N.apply_graph[f][op], N.apply_gexec[f][op]);
+}
+
 // What both solves start with: the whole factor in gpanel (multi-rank: collective), the
 // plan built, and the captured sweeps dropped when they point at another panel pool.
 static int64_t solve_prepare(Numeric& N) {
@@ -201,14 +214,7 @@ static int64_t solve_prepare(Numeric& N) {
     if (N.solve_ready && N.SP.panel_pool != N.gpanel) {
         N.SP.panel_pool = N.gpanel;  // gathered buffer allocated after the plan was built
         N.SPM.panel_pool = N.gpanel;
-        if (N.solve_gexec) (void)hipGraphExecDestroy(N.solve_gexec);
-        if (N.solve_graph) (void)hipGraphDestroy(N.solve_graph);
-        if (N.solve_multi_gexec) (void)hipGraphExecDestroy(N.solve_multi_gexec);
-        if (N.solve_multi_graph) (void)hipGraphDestroy(N.solve_multi_graph);
-        N.solve_gexec = nullptr;
-        N.solve_graph = nullptr;
-        N.solve_multi_gexec = nullptr;
-        N.solve_multi_graph = nullptr;
+        numeric_drop_solve_graphs(N);
     }
     if (!N.solve_ready) TRY(solve_build(N));
     return SC_OK;
@@ -377,6 +383,244 @@ int64_t numeric_solve_device_multi(Numeric& N, int32_t nrhs, const double* d_B, 
 
 int64_t numeric_solve_host_multi(Numeric& N, int32_t nrhs, const double* B, int64_t ldb, double* X, int64_t ldx) {
     return solve_multi(N, nrhs, B, ldb, X, ldx, hipMemcpyHostToDevice, hipMemcpyDeviceToHost);
+}
+
+// ---------------- factor operators (sc_factor_op) ----------------
+// L is the factor of P A P^T in the numbering of numeric_export; the kernels work in the
+// etree postorder of that, so the L-level ops permute by post alone, where the solves'
+// d_post is perm o post.  The half solves are the two halves of the solves' sweeps; the
+// products are their transposes (kernels.hip).  P and P^T need perm alone, which is a
+// gather by one of the two index arrays and a scatter by the other:
+//   P:   c[i] = b[perm[post[i]]],  x[post[i]] = c[i]        =>  x[k] = b[perm[k]]
+//   P^T: c[i] = b[post[i]],        x[perm[post[i]]] = c[i]  =>  x[perm[k]] = b[k]
+static int64_t apply_prepare(Numeric& N) {
+    TRY(solve_prepare(N));
+    if (!N.d_etpost) {
+        if (N.S->perm.empty())
+            N.d_etpost = N.d_post;
+        else
+            TRY(upload(N, N.S->post, N.d_etpost));
+    }
+    return SC_OK;
+}
+
+// Runs sweeps() on the handle's stream: eagerly (sc_debug_solve_eager), or as the op's
+// graph, captured at its first use (a single-stream chain, like the solves' graphs).
+template <class F>
+static int64_t apply_run(Numeric& N, int family, int32_t op, F&& sweeps) {
+    hipStream_t s0 = N.stream;
+    if (N.solve_eager) {
+        HIP_TRY(sweeps());
+        return SC_OK;
+    }
+    hipGraphExec_t& gexec = N.apply_gexec[family][op];
+    if (!gexec) {
+        HIP_TRY(hipStreamBeginCapture(s0, hipStreamCaptureModeThreadLocal));
+        hipError_t e = sweeps();
+        hipGraph_t g = nullptr;
+        hipError_t e2 = hipStreamEndCapture(s0, &g);
+        HIP_TRY(e);
+        HIP_TRY(e2);
+        N.apply_graph[family][op] = g;
+        HIP_TRY(hipGraphInstantiate(&gexec, g, nullptr, nullptr, 0));
+    }
+    HIP_TRY(hipGraphLaunch(gexec, s0));
+    return SC_OK;
+}
+
+static bool apply_needs_inverses(int32_t op) { return op == SC_OP_SOLVE_L || op == SC_OP_SOLVE_LT; }
+
+static int64_t apply_inverses(Numeric& N) {
+    if (N.inv_gen != N.factor_gen) {  // shared with the solves
+        HIP_TRY(launch_solve_inv(N.SP, N.d_sinv, N.n_sinv, N.d_sinv2, N.n_sinv2, N.stream));
+        N.inv_gen = N.factor_gen;
+    }
+    return SC_OK;
+}
+
+// in / out: the copy kinds of the caller's B and X (device or host memory)
+static int64_t apply_multi(Numeric& N, int32_t op, int32_t nrhs, const double* B, int64_t ldb, double* X, int64_t ldx,
+                           hipMemcpyKind in, hipMemcpyKind out) {
+    if (op == SC_OP_SOLVE_A) return solve_multi(N, nrhs, B, ldb, X, ldx, in, out);
+    if (!N.factored) return SC_ERR_STATE;
+    const int64_t st = numeric_status(N);
+    if (st != SC_OK) return st;
+    TRY(apply_prepare(N));
+    const int64_t n = N.S->n;
+    if (n == 0 || nrhs == 0) return SC_OK;
+    if (!N.multi_ready) TRY(solve_multi_build(N));
+    hipStream_t s0 = N.stream;
+    const SolvePlan& P = N.SPM;
+    double* io = N.d_mbuf;  // the handle's own panel, as in solve_multi
+    const size_t wide = (size_t)SOLVE_RHS * sizeof(double);
+    const int32_t* post = N.d_etpost;
+    auto zero_u = [&]() { return hipMemsetAsync(P.u, 0, (size_t)std::max<int64_t>(N.u_total, 1) * wide, s0); };
+    auto sweeps = [&]() -> hipError_t {
+        hipError_t e = hipSuccess;
+        switch (op) {
+            case SC_OP_SOLVE_L:  // the solve's forward half: y = L^-1 c
+                e = launch_permute_multi(P.c, io, post, n, false, s0);
+                if (e == hipSuccess) e = zero_u();
+                for (size_t i = 0; e == hipSuccess && i < N.solve_steps.size(); ++i) {
+                    const Numeric::SolveStep& t = N.solve_steps[i];
+                    e = launch_solve_fwd_gather_multi(P, N.d_sgather + t.gaoff, t.gacount, s0);
+                    if (e == hipSuccess) e = launch_solve_fwd_multi(P, N.d_sfwd + t.foff, t.fcount, s0);
+                }
+                if (e == hipSuccess) e = launch_permute_multi(P.y, io, post, n, true, s0);
+                break;
+            case SC_OP_SOLVE_LT:  // its backward half, in place on c
+                e = launch_permute_multi(P.c, io, post, n, false, s0);
+                for (size_t i = N.solve_steps.size(); e == hipSuccess && i-- > 0;) {
+                    const Numeric::SolveStep& t = N.solve_steps[i];
+                    e = launch_solve_gemv_multi(P, N.d_sgemv + t.goff, t.gcount, s0);
+                    if (e == hipSuccess) e = launch_solve_diag_multi(P, N.d_sdiag + t.doff, t.dcount, s0);
+                }
+                if (e == hipSuccess) e = launch_permute_multi(P.c, io, post, n, true, s0);
+                break;
+            case SC_OP_MUL_L:  // bottom-up: z in y (read-only), x accumulated in c and u
+                e = launch_permute_multi(P.y, io, post, n, false, s0);
+                if (e == hipSuccess) e = hipMemsetAsync(P.c, 0, (size_t)n * wide, s0);
+                if (e == hipSuccess) e = zero_u();
+                for (size_t i = 0; e == hipSuccess && i < N.solve_steps.size(); ++i) {
+                    const Numeric::SolveStep& t = N.solve_steps[i];
+                    e = launch_solve_fwd_gather_multi(P, N.d_sgather + t.gaoff, t.gacount, s0);
+                    if (e == hipSuccess) e = launch_mul_l_multi(P, N.d_sfwd + t.foff, t.fcount, s0);
+                }
+                if (e == hipSuccess) e = launch_permute_multi(P.c, io, post, n, true, s0);
+                break;
+            case SC_OP_MUL_LT:  // no front waits for another; the steps share the part buffer only
+                e = launch_permute_multi(P.y, io, post, n, false, s0);
+                for (size_t i = 0; e == hipSuccess && i < N.solve_steps.size(); ++i) {
+                    const Numeric::SolveStep& t = N.solve_steps[i];
+                    e = launch_mul_lt_gemv_multi(P, N.d_sgemv + t.goff, t.gcount, s0);
+                    if (e == hipSuccess) e = launch_mul_lt_diag_multi(P, N.d_sdiag + t.doff, t.dcount, s0);
+                }
+                if (e == hipSuccess) e = launch_permute_multi(P.c, io, post, n, true, s0);
+                break;
+            default: {  // SC_OP_PERM, SC_OP_PERM_T
+                const bool fwd = op == SC_OP_PERM;
+                e = launch_permute_multi(P.c, io, fwd ? N.d_post : post, n, false, s0);
+                if (e == hipSuccess) e = launch_permute_multi(P.c, io, fwd ? post : N.d_post, n, true, s0);
+            }
+        }
+        return e;
+    };
+    if (apply_needs_inverses(op)) TRY(apply_inverses(N));
+    const size_t colb = (size_t)n * sizeof(double);
+    for (int32_t j0 = 0; j0 < nrhs; j0 += SOLVE_RHS) {
+        const int nr = std::min<int32_t>(SOLVE_RHS, nrhs - j0);
+        HIP_TRY(hipMemcpy2DAsync(io, colb, B + (int64_t)j0 * ldb, (size_t)ldb * sizeof(double), colb, (size_t)nr, in,
+                                 s0));
+        // a partial panel: true zero columns, never the caller's memory
+        if (nr < SOLVE_RHS) HIP_TRY(hipMemsetAsync(io + (int64_t)nr * n, 0, (size_t)(SOLVE_RHS - nr) * colb, s0));
+        TRY(apply_run(N, 1, op, sweeps));
+        HIP_TRY(hipMemcpy2DAsync(X + (int64_t)j0 * ldx, (size_t)ldx * sizeof(double), io, colb, colb, (size_t)nr, out,
+                                 s0));
+        // host memory: one panel staged at a time
+        if (out != hipMemcpyDeviceToDevice) HIP_TRY(hipStreamSynchronize(s0));
+    }
+    HIP_TRY(hipStreamSynchronize(s0));
+    return SC_OK;
+}
+
+int64_t numeric_apply_device_multi(Numeric& N, int32_t op, int32_t nrhs, const double* d_B, int64_t ldb, double* d_X,
+                                   int64_t ldx) {
+    return apply_multi(N, op, nrhs, d_B, ldb, d_X, ldx, hipMemcpyDeviceToDevice, hipMemcpyDeviceToDevice);
+}
+
+int64_t numeric_apply_host_multi(Numeric& N, int32_t op, int32_t nrhs, const double* B, int64_t ldb, double* X,
+                                 int64_t ldx) {
+    return apply_multi(N, op, nrhs, B, ldb, X, ldx, hipMemcpyHostToDevice, hipMemcpyDeviceToHost);
+}
+
+int64_t numeric_apply_device(Numeric& N, int32_t op, const double* d_b, double* d_x) {
+    if (op == SC_OP_SOLVE_A) return numeric_solve_device(N, d_b, d_x);
+    const int64_t n = N.S->n;
+    // the products have panel kernels only: a panel of one column
+    if (op == SC_OP_MUL_L || op == SC_OP_MUL_LT) return numeric_apply_device_multi(N, op, 1, d_b, n, d_x, n);
+    if (!N.factored) return SC_ERR_STATE;
+    const int64_t st = numeric_status(N);
+    if (st != SC_OK) return st;
+    TRY(apply_prepare(N));
+    if (n == 0) return SC_OK;
+    hipStream_t s0 = N.stream;
+    double* io = N.d_sbuf;  // the handle's own vector, as in numeric_solve_device
+    const int32_t* post = N.d_etpost;
+    auto sweeps = [&]() -> hipError_t {
+        hipError_t e = hipSuccess;
+        switch (op) {
+            case SC_OP_SOLVE_L:
+                e = launch_permute(N.SP.c, io, post, n, false, s0);
+                if (e == hipSuccess)
+                    e = hipMemsetAsync(N.SP.u, 0, (size_t)std::max<int64_t>(N.u_total, 1) * sizeof(double), s0);
+                for (size_t i = 0; e == hipSuccess && i < N.solve_steps.size(); ++i) {
+                    const Numeric::SolveStep& t = N.solve_steps[i];
+                    e = launch_solve_fwd_gather(N.SP, N.d_sgather + t.gaoff, t.gacount, s0);
+                    if (e == hipSuccess) e = launch_solve_fwd(N.SP, N.d_sfwd + t.foff, t.fcount, s0);
+                }
+                if (e == hipSuccess) e = launch_permute(io, N.SP.y, post, n, true, s0);
+                break;
+            case SC_OP_SOLVE_LT:
+                e = launch_permute(N.SP.c, io, post, n, false, s0);
+                for (size_t i = N.solve_steps.size(); e == hipSuccess && i-- > 0;) {
+                    const Numeric::SolveStep& t = N.solve_steps[i];
+                    e = launch_solve_gemv(N.SP, N.d_sgemv + t.goff, t.gcount, s0);
+                    if (e == hipSuccess) e = launch_solve_diag(N.SP, N.d_sdiag + t.doff, t.dcount, s0);
+                }
+                if (e == hipSuccess) e = launch_permute(io, N.SP.c, post, n, true, s0);
+                break;
+            default: {  // SC_OP_PERM, SC_OP_PERM_T
+                const bool fwd = op == SC_OP_PERM;
+                e = launch_permute(N.SP.c, io, fwd ? N.d_post : post, n, false, s0);
+                if (e == hipSuccess) e = launch_permute(io, N.SP.c, fwd ? post : N.d_post, n, true, s0);
+            }
+        }
+        return e;
+    };
+    if (apply_needs_inverses(op)) TRY(apply_inverses(N));
+    const size_t nb = (size_t)n * sizeof(double);
+    if (d_b != io) HIP_TRY(hipMemcpyAsync(io, d_b, nb, hipMemcpyDeviceToDevice, s0));
+    TRY(apply_run(N, 0, op, sweeps));
+    if (d_x != io) HIP_TRY(hipMemcpyAsync(d_x, io, nb, hipMemcpyDeviceToDevice, s0));
+    HIP_TRY(hipStreamSynchronize(s0));
+    return SC_OK;
+}
+
+int64_t numeric_apply_host(Numeric& N, int32_t op, const double* b, double* x) {
+    if (op == SC_OP_SOLVE_A) return numeric_solve_host(N, b, x);
+    const int64_t n = N.S->n;
+    if (op == SC_OP_MUL_L || op == SC_OP_MUL_LT) return numeric_apply_host_multi(N, op, 1, b, n, x, n);
+    if (!N.factored) return SC_ERR_STATE;
+    const int64_t st = numeric_status(N);
+    if (st != SC_OK) return st;
+    HIP_TRY(hipSetDevice(N.device));
+    if (!N.solve_ready) TRY(solve_build(N));
+    const size_t nb = (size_t)n * sizeof(double);
+    if (nb == 0) return SC_OK;
+    HIP_TRY(hipMemcpy(N.d_sbuf, b, nb, hipMemcpyHostToDevice));
+    TRY(numeric_apply_device(N, op, N.d_sbuf, N.d_sbuf));
+    HIP_TRY(hipMemcpy(x, N.d_sbuf, nb, hipMemcpyDeviceToHost));
+    return SC_OK;
+}
+
+int64_t numeric_logdet(Numeric& N, double* logdet) {
+    if (!N.factored) return SC_ERR_STATE;
+    const int64_t st = numeric_status(N);
+    if (st != SC_OK) return st;
+    TRY(solve_prepare(N));
+    const int64_t n = N.S->n;
+    if (n == 0) {
+        *logdet = 0.0;  // the empty product
+        return SC_OK;
+    }
+    // scratch in the single-vector plan's c and y (2 n doubles, no solve in flight): the
+    // per-workgroup sums, then the result
+    double* part = N.SP.c;
+    double* out = part + (n + LOGDET_NT - 1) / LOGDET_NT;
+    HIP_TRY(launch_logdet(N.SP, N.S->ns, n, part, out, N.stream));
+    HIP_TRY(hipMemcpyAsync(logdet, out, sizeof(double), hipMemcpyDeviceToHost, N.stream));
+    HIP_TRY(hipStreamSynchronize(N.stream));
+    return SC_OK;
 }
 
 }  // namespace sc
