@@ -34,7 +34,7 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define SC_VERSION 121 /* still 1.2.1, additive: the factor operators sc_apply_host / sc_apply_device / sc_apply_host_multi / sc_apply_device_multi (enum sc_factor_op) and sc_logdet; still 1.2.1, additive: sc_solve_host_multi / sc_solve_device_multi (nrhs right-hand sides); 1.2.1:small merged fronts amalgamated past relax_wmax (different supernode partition of some inputs, same L); 1.2.0: persistent slab chain options removed; panel_prefactor, dist_local_pieces and SC_ORDER_AMD added; out-of-range lookahead / inner_order / ordering rejected */
+#define SC_VERSION 121 /* still 1.2.1, additive: selected inversion sc_selinv / sc_selinv_diag_host / sc_selinv_diag_device / sc_selinv_export / sc_selinv_flops; still 1.2.1, additive: the factor operators sc_apply_host / sc_apply_device / sc_apply_host_multi / sc_apply_device_multi (enum sc_factor_op) and sc_logdet; still 1.2.1, additive: sc_solve_host_multi / sc_solve_device_multi (nrhs right-hand sides); 1.2.1:small merged fronts amalgamated past relax_wmax (different supernode partition of some inputs, same L); 1.2.0: persistent slab chain options removed; panel_prefactor, dist_local_pieces and SC_ORDER_AMD added; out-of-range lookahead / inner_order / ordering rejected */
 
 enum sc_status {
     SC_OK = 0,
@@ -338,6 +338,52 @@ int64_t sc_apply_host_multi(sc_numeric* num, int32_t op, int32_t nrhs, const dou
  * a fixed order: bitwise repeatable across calls and handles.  Status and collective
  * rules of the solves (> 0: *logdet untouched). */
 int64_t sc_logdet(sc_numeric* num, double* logdet);
+
+/* Selected inversion on the GPU: the entries of A^-1 that lie on the pattern of L (the
+ * marginal variances diag(A^-1) and the covariances between neighbours of a precision
+ * matrix A; CHOLMOD-family users know it as the sparse inverse subset).  Takahashi
+ * recurrence over the supernodal factor, top-down, as fp64 MFMA products on the fronts
+ * already on the device: with Z = (P A P^T)^-1, per 128-column block K of a front's
+ * pivots, R the front rows after it and X = inv(L_KK),
+ *     W = L_RK X,   Z_RK = -Z_RR W,   Z_KK = X^T X - W^T Z_RK.
+ * sc_selinv computes every selected entry into a second panel arena of the handle (the
+ * "Z panel", the layout of the L panels), synchronously, on the handle's stream.  L is
+ * not overwritten: solves, operators and sc_logdet keep working, with the same bits.
+ * Results are bitwise repeatable across calls and handles (no atomics, fixed order).
+ * Numbering: sc_selinv_export returns Z in sc_export_L's layout and numbering (the order
+ * of P A P^T): Zx[p] = Z[Li[p], j] for p in [Lp[j], Lp[j+1]), Z[k, l] = A^-1[perm[k],
+ * perm[l]] with perm = sc_symbolic_perm; any of the three arrays may be NULL.  The
+ * diagonal accessors return diag(A^-1) in A's OWN order, length n (host / device memory).
+ * An accessor computes first when the Z panel does not belong to the current
+ * factorization (never called, or a newer sc_factor since), so it never serves a stale
+ * result.  Entries of Z at relaxed-zero positions of the supernodes (L = 0 there, Z in
+ * general not) are computed and kept in the Z panel, but are outside the exported pattern.
+ * Status rules of the solves: SC_ERR_STATE before a factorization; a failed factorization
+ * returns its status > 0 and computes nothing (outputs untouched); n == 0: SC_OK;
+ * SC_ERR_ARG for a null handle or output.  Multi-rank and emulated handles: SC_ERR_NOTIMPL
+ * with a message in sc_last_error -- the recurrence keeps a front's Z_II block in the work
+ * arena, and those arenas are per rank.
+ * Device memory, all counted in sc_numeric_memory info[0], allocated at the first call and
+ * kept until sc_free_numeric: the Z panel (info[1] bytes again: the factor's size, 26.4 GB
+ * for the 128^3 Laplacian), the W scratch (8 bytes times the largest sum of nr nb over the
+ * blocks of one step, at most the largest front's m times 128 for the upper levels), the
+ * partials of the deep Z_KK products (a product with K = nb + nr > 512 is cut into
+ * ceil(K / 256) chunks; 32 KiB per chunk and 64 x 64 tile of the block's lower triangle,
+ * the largest sum over one step) and the task lists (16 bytes per block, 8 bytes per 64-row
+ * tile of a block's rows below, 16 bytes per Z_KK tile and chunk plus 16 per tile that is
+ * cut, 16 bytes per 64 x 64 tile of a contribution block), besides the solves' plan when no solve has run yet.  A later call
+ * allocates nothing.  The work arena is only borrowed: the next factorization reuses it.
+ * The first call after a factorization also forms the diagonal-block inverses the solves
+ * store in L's unused upper triangles, if no solve has yet. */
+int64_t sc_selinv(sc_numeric* num);
+int64_t sc_selinv_diag_host(sc_numeric* num, double* d);
+int64_t sc_selinv_diag_device(sc_numeric* num, double* d_d);
+int64_t sc_selinv_export(sc_numeric* num, int64_t* Lp, int32_t* Li, double* Zx);
+/* Dense flops the sweep executes, from the symbolic structure alone (no device): the sum
+ * over every supernode (m front rows, w pivots) and every block k0 = 0, 128, .. < w, with
+ * nb = min(128, w - k0) and nr = m - k0 - nb, of
+ *     2 nr nb^2  (W)  +  2 nr^2 nb  (Z_RK)  +  nb (nb + 1) (nb + nr)  (Z_KK, lower triangle). */
+int64_t sc_selinv_flops(const sc_symbolic* sym, double* flops);
 
 /* ---------------- reference-API helpers (host) ----------------
  * Each mirrors one reference function, with int64 column pointers. */

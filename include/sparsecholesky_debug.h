@@ -29,6 +29,16 @@ int64_t sc_debug_syrk(double* dC, int32_t ldc, const double* dA, int32_t lda, in
 int64_t sc_debug_time_factor(sc_numeric* num, const double* d_Ax, int32_t reps, double* best_ms);
 /* Debug: eager = 1 launches the solve sweeps directly instead of replaying their graph. */
 int64_t sc_debug_solve_eager(sc_numeric* num, int32_t eager);
+/* Selected inversion: profile = 1 makes the next sc_selinv calls record a HIP event after
+ * every launch; ms[4] (may be NULL) receives the split of the last profiled call over the
+ * kernel classes W, Z_RK, Z_KK and push, milliseconds. */
+int64_t sc_debug_selinv_times(sc_numeric* num, int32_t profile, double* ms);
+/* sc_export_L_cols of the selected inverse: columns [j0, j1) of Z straight from the Z
+ * panel (the column's front rows from j down, relaxed-zero positions included), for
+ * factors too large for sc_selinv_export.  Computes first like the sc_selinv accessors;
+ * returns the entry count; a failed factorization's status > 0 cannot be told from a
+ * count, so check sc_selinv first. */
+int64_t sc_debug_selinv_cols(sc_numeric* num, int64_t j0, int64_t j1, int64_t* cp, int32_t* ri, double* rx);
 /* Chain launches (runs of single small-front levels): enable = 1 makes the next
  * eager factorizations record 8 shader-clock stamps per chained front (phase
  * boundaries); enable = 0 copies up to cap of them to out.  Returns the count. */

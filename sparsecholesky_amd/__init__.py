@@ -138,6 +138,11 @@ _SIGS = [
     ("sc_apply_device_multi", _I64, [_P, _I32, _I32, _P, _I64, _P, _I64]),
     ("sc_apply_host_multi", _I64, [_P, _I32, _I32, _P, _I64, _P, _I64]),
     ("sc_logdet", _I64, [_P, _P]),
+    ("sc_selinv", _I64, [_P]),
+    ("sc_selinv_diag_host", _I64, [_P, _P]),
+    ("sc_selinv_diag_device", _I64, [_P, _P]),
+    ("sc_selinv_export", _I64, [_P, _P, _P, _P]),
+    ("sc_selinv_flops", _I64, [_P, C.POINTER(_D)]),
     ("sc_etree", _I64, [_I64, _P, _P, _P]),
     ("sc_post_order", _I64, [_I64, _P, _P]),
     ("sc_col_count", _I64, [_I64, _P, _P, _P, _P, _P]),
@@ -166,6 +171,8 @@ _SIGS = [
     ("sc_debug_chain_stamps", _I64, [_P, _I32, _P, _I64]),
     ("sc_debug_time_factor", _I64, [_P, C.c_void_p, _I32, C.POINTER(_D)]),
     ("sc_debug_solve_eager", _I64, [_P, _I32]),
+    ("sc_debug_selinv_times", _I64, [_P, _I32, _P]),
+    ("sc_debug_selinv_cols", _I64, [_P, _I64, _I64, _P, _P, _P]),
     ("sc_debug_hwid", _I64, [_I32, _I32, _I32, _P]),
     ("sc_debug_contention", _I64, [_I32, _I32, _I32, _I32, _I32, _I32, _P]),
     ("sc_debug_schedule_digest", _I64, [_P, _I32, _I32, _I32, _P, _I64]),
@@ -501,6 +508,12 @@ class Symbolic:
     def flops(self) -> float:
         return float(lib().sc_flops(self.h))
 
+    def selinv_flops(self) -> float:
+        """Dense flops of the selected inversion's sweep (C ABI sc_selinv_flops)."""
+        v = C.c_double()
+        _check(lib().sc_selinv_flops(self.h, C.byref(v)), "selinv_flops")
+        return v.value
+
     def pattern(self):
         Lp = np.zeros(self.n + 1, dtype=np.int64)
         Li = np.zeros(max(self.nnz_L, 1), dtype=np.int32)
@@ -822,6 +835,60 @@ class Numeric:
         if st > 0:
             raise LibraryError(f"logdet: A is not positive definite (column {st})")
         return v.value
+
+    def selinv(self) -> int:
+        """Selected inversion: every entry of A^-1 on the pattern of L into the handle's Z
+        panel on the GPU (synchronous; single-device handles).  The accessors below call it
+        themselves when no result of the current factorization exists."""
+        st = _check(lib().sc_selinv(self.h), "selinv")
+        if st > 0:
+            raise LibraryError(f"selinv: A is not positive definite (column {st})")
+        return st
+
+    def inverse_diagonal(self) -> np.ndarray:
+        """diag(A^-1), in A's own order (length n)."""
+        d = np.zeros(self.symb.n, dtype=np.float64)
+        st = _check(lib().sc_selinv_diag_host(self.h, _ptr(d)), "inverse_diagonal")
+        if st > 0:
+            raise LibraryError(f"inverse_diagonal: A is not positive definite (column {st})")
+        return d
+
+    def inverse_diagonal_device(self, d_ptr: int) -> int:
+        """diag(A^-1), in A's own order, into n doubles of device memory at ``d_ptr``."""
+        st = _check(lib().sc_selinv_diag_device(self.h, C.c_void_p(d_ptr)), "inverse_diagonal_device")
+        if st > 0:
+            raise LibraryError(f"inverse_diagonal_device: A is not positive definite (column {st})")
+        return st
+
+    def selected_inverse(self) -> tuple:
+        """(Lp, Li, Zx): Z = (P A P^T)^-1 on the pattern of L, in :meth:`export`'s layout and
+        numbering: Zx[p] = Z[Li[p], j] for p in [Lp[j], Lp[j+1]), Z[k, l] = A^-1[perm[k], perm[l]]."""
+        n = self.symb.n
+        nz = self.symb.nnz_L
+        Lp = np.zeros(n + 1, dtype=np.int64)
+        Li = np.zeros(max(nz, 1), dtype=np.int32)
+        Zx = np.zeros(max(nz, 1), dtype=np.float64)
+        st = _check(lib().sc_selinv_export(self.h, _ptr(Lp), _ptr(Li), _ptr(Zx)), "selected_inverse")
+        if st > 0:
+            raise LibraryError(f"selected_inverse: A is not positive definite (column {st})")
+        return Lp, Li[:nz], Zx[:nz]
+
+    def selected_inverse_cols(self, j0: int, j1: int) -> tuple:
+        """Columns [j0, j1) of Z from the Z panel, in :meth:`export_cols`'s form (debug hook
+        sc_debug_selinv_cols; for factors too large for :meth:`selected_inverse`)."""
+        cp = np.zeros(j1 - j0 + 1, dtype=np.int64)
+        tot = _check(lib().sc_debug_selinv_cols(self.h, j0, j1, _ptr(cp), None, None), "selected_inverse_cols")
+        ri = np.zeros(max(tot, 1), dtype=np.int32)
+        rx = np.zeros(max(tot, 1), dtype=np.float64)
+        _check(lib().sc_debug_selinv_cols(self.h, j0, j1, _ptr(cp), _ptr(ri), _ptr(rx)), "selected_inverse_cols")
+        return cp, ri[:tot], rx[:tot]
+
+    def selinv_times(self, profile: bool = False) -> dict:
+        """Time split (ms) of the last profiled :meth:`selinv` over its kernel classes;
+        ``profile`` switches the per-launch HIP events of the next calls on or off."""
+        t = np.zeros(4)
+        _check(lib().sc_debug_selinv_times(self.h, 1 if profile else 0, _ptr(t)), "selinv_times")
+        return dict(W=float(t[0]), Z_RK=float(t[1]), Z_KK=float(t[2]), push=float(t[3]))
 
     def __del__(self):
         h = getattr(self, "h", None)

@@ -499,6 +499,75 @@ int64_t sc_logdet(sc_numeric* num, double* logdet) {
     return rc;
 }
 
+// ---- selected inversion ----
+static int64_t selinv_args(sc_numeric* num, const void* out, const char* who, const char* what) {
+    if (!num || !num->N) {
+        g_last_error = std::string(who) + ": null handle";
+        return SC_ERR_ARG;
+    }
+    if (!out) {
+        g_last_error = std::string(who) + ": null " + what;
+        return SC_ERR_ARG;
+    }
+    return SC_OK;
+}
+
+int64_t sc_selinv(sc_numeric* num) {
+    int64_t rc = selinv_args(num, num, "sc_selinv", "handle");
+    if (rc != SC_OK) return rc;
+    rc = sc::numeric_selinv(*num->N);
+    if (rc < 0) g_last_error = num->N->err;
+    return rc;
+}
+
+int64_t sc_selinv_diag_host(sc_numeric* num, double* d) {
+    int64_t rc = selinv_args(num, d, "sc_selinv_diag_host", "d");
+    if (rc != SC_OK) return rc;
+    rc = sc::numeric_selinv_diag_host(*num->N, d);
+    if (rc < 0) g_last_error = num->N->err;
+    return rc;
+}
+
+int64_t sc_selinv_diag_device(sc_numeric* num, double* d_d) {
+    int64_t rc = selinv_args(num, d_d, "sc_selinv_diag_device", "d_d");
+    if (rc != SC_OK) return rc;
+    rc = sc::numeric_selinv_diag_device(*num->N, d_d);
+    if (rc < 0) g_last_error = num->N->err;
+    return rc;
+}
+
+int64_t sc_selinv_export(sc_numeric* num, int64_t* Lp, int32_t* Li, double* Zx) {
+    int64_t rc = selinv_args(num, num, "sc_selinv_export", "handle");
+    if (rc != SC_OK) return rc;
+    rc = sc::numeric_selinv_export(*num->N, Lp, Li, Zx);
+    if (rc < 0) g_last_error = num->N->err;
+    return rc;
+}
+
+int64_t sc_selinv_flops(const sc_symbolic* sym, double* flops) {
+    if (!sym || !flops) {
+        g_last_error = !sym ? "sc_selinv_flops: null symbolic" : "sc_selinv_flops: null flops";
+        return SC_ERR_ARG;
+    }
+    *flops = sc::selinv_flops(sym->S);
+    return SC_OK;
+}
+
+int64_t sc_debug_selinv_times(sc_numeric* num, int32_t profile, double* ms) {
+    if (!num || !num->N) return SC_ERR_ARG;
+    num->N->sel_profile = profile != 0;
+    if (ms)
+        for (int i = 0; i < 4; ++i) ms[i] = num->N->sel_ms[i];
+    return SC_OK;
+}
+
+int64_t sc_debug_selinv_cols(sc_numeric* num, int64_t j0, int64_t j1, int64_t* cp, int32_t* ri, double* rx) {
+    if (!num || !num->N) return SC_ERR_ARG;
+    const int64_t rc = sc::numeric_selinv_export_cols(*num->N, j0, j1, cp, ri, rx);
+    if (rc < 0) g_last_error = num->N->err;
+    return rc;
+}
+
 // ---- reference-API helpers ----
 int64_t sc_etree(int64_t n, const int64_t* Ap, const int32_t* Ai, int32_t* parent) {
     if (n < 0 || !Ap || !parent) return SC_ERR_ARG;

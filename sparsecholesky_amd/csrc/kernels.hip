@@ -3026,4 +3026,322 @@ hipError_t launch_permute_multi(double* c, double* io, const int32_t* perm, int6
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------
+// Selected inversion: Z = (P A P^T)^-1 on the pattern of L, by the Takahashi recurrence
+// over the supernodal factor.  Per 128-column block K = [k0, k1)
+// of a front (m rows, w pivots), R = front positions [k1, m), X = inv(L_KK):
+//   W    = L_RK X            sel_w_kernel
+//   Z_RK = -Z_RR W           sel_zrk_kernel (the hot product)
+//   Z_KK = X^T X - W^T Z_RK  sel_zkk_kernel
+// blocks of a front last to first, fronts top-down; after a level, sel_push_kernel copies
+// every child's Z_II out of its parent's front.  The three products share one tile body:
+// a workgroup of NW waves owns 16 NW output rows x 16 NT columns (W and Z_RK: SEL_BM = 64
+// rows x all nb columns; Z_KK: 64 x 64; four waves each), K staged
+// SEL_BK = 16 deep through LDS (the next round's loads in flight under the products),
+// wave v the rows 16 v .. on v_mfma_f64_16x16x4_f64 (A: row lane & 15, k = lane >> 4; B: k =
+// lane >> 4, column lane & 15; D: row (lane >> 4) + 4 reg, column lane & 15).  Operands
+// come through element functors, so the row and column tails (any nr, nb in [1, 128])
+// are range checks of the loads.  One workgroup per output tile, K in ascending order:
+// no atomics, bitwise repeatable.  L is only read: X through its stored form (X(i, k),
+// k < i, at block row k, column i -- the strict upper triangle launch_solve_inv fills --
+// and the diagonal as 1 / L(i, i)), L_RK from rows below the block.
+// ---------------------------------------------------------------------------
+// LDS row strides of 16 mod 32 doubles (rows + 16): the k = lane >> 4 rows of a half-wave's
+// operand read fall into disjoint banks.
+
+// Element (p, q) of a front's symmetric Z (front positions; any order): columns < w from
+// the Z panel, whose pivot square holds both triangles; rows < w of later columns from the
+// panel transposed; the rest from Z_II (both triangles).
+__device__ __forceinline__ double sel_zfront(const double* __restrict__ zp, const double* __restrict__ zi, int m,
+                                             int w, int p, int q) {
+    if (q < w) return zp[(int64_t)q * m + p];
+    if (p < w) return zp[(int64_t)p * m + q];
+    return zi[(int64_t)(q - w) * (m - w) + (p - w)];
+}
+
+// X(i, k) of the block at lblk (its diagonal element (0, 0)), i, k < nb
+__device__ __forceinline__ double sel_x(const double* __restrict__ lblk, int m, int i, int k) {
+    if (k > i) return 0.0;
+    const double v = lblk[(int64_t)i * m + k];
+    return k == i ? 1.0 / v : v;
+}
+
+// acc += A(row0 .. row0 + 16 NW, 0 .. K) B(0 .. K, 0 .. 16 NT) restricted to rows < M and
+// columns < N, by a workgroup of NW waves; fa(i, k), fb(k, j) give the elements.  AKF / BKF:
+// consecutive lanes load along k (else along the row / column index): whichever is
+// contiguous in memory.  As: SEL_BK x (16 NW + 16), Bs: SEL_BK x (16 NT + 16) doubles.
+template <int NW, int NT, bool AKF, bool BKF, class FA, class FB>
+__device__ __forceinline__ void sel_mma(int M, int N, int K, int row0, FA fa, FB fb, double4_t (&acc)[NT],
+                                        double* As, double* Bs) {
+    constexpr int BM = 16 * NW, NTH = 64 * NW, LDA = BM + 16, BN = 16 * NT, LDB = BN + 16;
+    constexpr int NA = BM * SEL_BK / NTH, NBL = SEL_BK * BN / NTH;
+    static_assert(NA * NTH == BM * SEL_BK && NBL * NTH == SEL_BK * BN, "whole loads per thread");
+    const int tid = threadIdx.x, lane = tid & 63, wv = wave_id();
+    const int il = lane & 15, kq = lane >> 4;
+    double ra[NA], rb[NBL];
+    auto fetch = [&](int kk) {
+#pragma unroll
+        for (int q = 0; q < NA; ++q) {
+            const int e = tid + NTH * q;
+            const int i = AKF ? e >> 4 : e % BM, k = AKF ? e & 15 : e / BM;
+            ra[q] = (row0 + i < M && kk + k < K) ? fa(row0 + i, kk + k) : 0.0;
+        }
+#pragma unroll
+        for (int q = 0; q < NBL; ++q) {
+            const int e = tid + NTH * q;
+            const int j = BKF ? e >> 4 : e % BN, k = BKF ? e & 15 : e / BN;
+            rb[q] = (j < N && kk + k < K) ? fb(kk + k, j) : 0.0;
+        }
+    };
+    fetch(0);
+    for (int kk = 0; kk < K; kk += SEL_BK) {
+#pragma unroll
+        for (int q = 0; q < NA; ++q) {
+            const int e = tid + NTH * q;
+            const int i = AKF ? e >> 4 : e % BM, k = AKF ? e & 15 : e / BM;
+            As[k * LDA + i] = ra[q];
+        }
+#pragma unroll
+        for (int q = 0; q < NBL; ++q) {
+            const int e = tid + NTH * q;
+            const int j = BKF ? e >> 4 : e % BN, k = BKF ? e & 15 : e / BN;
+            Bs[k * LDB + j] = rb[q];
+        }
+        __syncthreads();
+        if (kk + SEL_BK < K) fetch(kk + SEL_BK);
+        if (row0 + 16 * wv < M) {  // wave-uniform
+#pragma unroll
+            for (int ks = 0; ks < SEL_BK / 4; ++ks) {
+                const double a = As[(4 * ks + kq) * LDA + 16 * wv + il];
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt) {
+                    if (16 * nt >= N) continue;  // wave-uniform
+                    acc[nt] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, Bs[(4 * ks + kq) * LDB + 16 * nt + il], acc[nt], 0,
+                                                                  0, 0);
+                }
+            }
+        }
+        __syncthreads();
+    }
+}
+
+struct SelGeom {
+    int s, k0, m, w, nb, k1, nr;
+    int64_t po;
+};
+__device__ __forceinline__ SelGeom sel_geom(const SelPlan& P, const SelBlk& b) {
+    SelGeom g;
+    g.s = b.s;
+    g.k0 = b.k0;
+    g.m = P.sn_m[b.s];
+    g.w = P.sn_start[b.s + 1] - P.sn_start[b.s];
+    g.nb = min(SOLVE_NB, g.w - g.k0);
+    g.k1 = g.k0 + g.nb;
+    g.nr = g.m - g.k1;
+    g.po = P.panel_off[b.s];
+    return g;
+}
+
+constexpr int SEL_NT_WIDE = SOLVE_NB / 16;  // all nb columns of a block in one workgroup
+
+__global__ __launch_bounds__(64 * SEL_NW) void sel_w_kernel(SelPlan P, const int2* __restrict__ tiles) {
+    __shared__ double As[SEL_BK * (SEL_BM + 16)], Bs[SEL_BK * (SOLVE_NB + 16)];
+    const int2 t = tiles[blockIdx.x];
+    const SelBlk b = P.blk[t.x];
+    const SelGeom g = sel_geom(P, b);
+    const int row0 = SEL_BM * t.y, m = g.m;
+    const double* __restrict__ lrk = P.lpanel + g.po + (int64_t)g.k0 * m + g.k1;  // L(k1 + i, k0 + k)
+    const double* __restrict__ lblk = P.lpanel + g.po + (int64_t)g.k0 * m + g.k0;
+    double4_t acc[SEL_NT_WIDE];
+#pragma unroll
+    for (int nt = 0; nt < SEL_NT_WIDE; ++nt) acc[nt] = double4_t {0.0, 0.0, 0.0, 0.0};
+    sel_mma<SEL_NW, SEL_NT_WIDE, false, false>(
+        g.nr, g.nb, g.nb, row0, [&](int i, int k) { return lrk[(int64_t)k * m + i]; },
+        [&](int k, int j) { return sel_x(lblk, m, k, j); }, acc, As, Bs);
+    const int lane = threadIdx.x & 63, wv = wave_id(), il = lane & 15;
+    double* __restrict__ W = P.wbuf + b.woff;
+#pragma unroll
+    for (int nt = 0; nt < SEL_NT_WIDE; ++nt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int i = row0 + 16 * wv + MFMA_F64_ROW(lane, r), j = 16 * nt + il;
+            if (i < g.nr && j < g.nb) W[(int64_t)j * g.nr + i] = acc[nt][r];
+        }
+}
+
+__global__ __launch_bounds__(64 * SEL_NW) void sel_zrk_kernel(SelPlan P, const int2* __restrict__ tiles) {
+    __shared__ double As[SEL_BK * (SEL_BM + 16)], Bs[SEL_BK * (SOLVE_NB + 16)];
+    const int2 t = tiles[blockIdx.x];
+    const SelBlk b = P.blk[t.x];
+    const SelGeom g = sel_geom(P, b);
+    const int row0 = SEL_BM * t.y, m = g.m, w = g.w, k1 = g.k1, nr = g.nr;
+    double* __restrict__ zp = P.zpanel + g.po;
+    const double* __restrict__ zi = P.zii + P.cb_off[g.s];
+    const double* __restrict__ W = P.wbuf + b.woff;
+    double4_t acc[SEL_NT_WIDE];
+#pragma unroll
+    for (int nt = 0; nt < SEL_NT_WIDE; ++nt) acc[nt] = double4_t {0.0, 0.0, 0.0, 0.0};
+    // Z_RR(i, k) = front element (k1 + i, k1 + k): never an entry of this step's columns K
+    sel_mma<SEL_NW, SEL_NT_WIDE, false, true>(
+        nr, g.nb, nr, row0, [&](int i, int k) { return sel_zfront(zp, zi, m, w, k1 + i, k1 + k); },
+        [&](int k, int j) { return W[(int64_t)j * nr + k]; }, acc, As, Bs);
+    const int lane = threadIdx.x & 63, wv = wave_id(), il = lane & 15;
+#pragma unroll
+    for (int nt = 0; nt < SEL_NT_WIDE; ++nt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int i = row0 + 16 * wv + MFMA_F64_ROW(lane, r), j = 16 * nt + il;
+            if (i < nr && j < g.nb) {
+                const int p = k1 + i, q = g.k0 + j;
+                const double v = -acc[nt][r];
+                zp[(int64_t)q * m + p] = v;
+                if (p < w) zp[(int64_t)p * m + q] = v;  // the pivot square's mirror (row q of column p)
+            }
+        }
+}
+
+// Tasks (block, 2 ti + tj, chunk, slot).  slot < 0: the whole K range, written to both
+// triangles of the block's square.  Else K chunk [SEL_KC chunk, ..) of a deep product:
+// the 64 x 64 partial goes to part + 4096 slot, and sel_zkk_reduce_kernel adds a tile's
+// partials in chunk order (a fixed order: still no atomics).
+__global__ __launch_bounds__(256) void sel_zkk_kernel(SelPlan P, const int4* __restrict__ tasks) {
+    __shared__ double As[SEL_BK * (SEL_KT + 16)], Bs[SEL_BK * (SEL_KT + 16)];
+    const int4 t = tasks[blockIdx.x];
+    const SelBlk b = P.blk[t.x];
+    const SelGeom g = sel_geom(P, b);
+    const int row0 = SEL_KT * (t.y >> 1), col0 = SEL_KT * (t.y & 1), m = g.m, nb = g.nb, nr = g.nr;
+    double* __restrict__ zp = P.zpanel + g.po;
+    const double* __restrict__ zrk = zp + (int64_t)g.k0 * m + g.k1;  // Z_RK(r, j) at zrk[j m + r]
+    const double* __restrict__ lblk = P.lpanel + g.po + (int64_t)g.k0 * m + g.k0;
+    const double* __restrict__ W = P.wbuf + b.woff;
+    const int kb = t.w < 0 ? 0 : SEL_KC * t.z, ke = t.w < 0 ? nb + nr : min(nb + nr, kb + SEL_KC);
+    double4_t acc[4];
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt) acc[nt] = double4_t {0.0, 0.0, 0.0, 0.0};
+    // one K range: the nb terms of X^T X, then the nr terms of -W^T Z_RK
+    sel_mma<SEL_KT / 16, SEL_KT / 16, true, true>(
+        nb, nb - col0, ke - kb, row0,
+        [&](int i, int k) {
+            k += kb;
+            return k < nb ? sel_x(lblk, m, k, i) : -W[(int64_t)i * nr + (k - nb)];
+        },
+        [&](int k, int j) {
+            k += kb;
+            return k < nb ? sel_x(lblk, m, k, col0 + j) : zrk[(int64_t)(col0 + j) * m + (k - nb)];
+        },
+        acc, As, Bs);
+    const int lane = threadIdx.x & 63, wv = wave_id(), il = lane & 15;
+    double* __restrict__ zkk = zp + (int64_t)g.k0 * m + g.k0;
+    double* __restrict__ part = P.part + (int64_t)max(t.w, 0) * (SEL_KT * SEL_KT);
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int il_ = 16 * wv + MFMA_F64_ROW(lane, r), jl = 16 * nt + il;
+            const int i = row0 + il_, j = col0 + jl;
+            if (t.w >= 0) {
+                part[jl * SEL_KT + il_] = acc[nt][r];  // rows / columns past nb hold exact zeros
+            } else if (i < nb && j <= i) {  // the lower triangle decides both triangles: an exactly symmetric block
+                zkk[(int64_t)j * m + i] = acc[nt][r];
+                zkk[(int64_t)i * m + j] = acc[nt][r];
+            }
+        }
+}
+
+// Tasks (block, 2 ti + tj, first slot, chunks): the tile's partials summed in chunk order.
+__global__ __launch_bounds__(256) void sel_zkk_reduce_kernel(SelPlan P, const int4* __restrict__ tasks) {
+    const int4 t = tasks[blockIdx.x];
+    const SelBlk b = P.blk[t.x];
+    const SelGeom g = sel_geom(P, b);
+    const int row0 = SEL_KT * (t.y >> 1), col0 = SEL_KT * (t.y & 1), m = g.m;
+    double* __restrict__ zkk = P.zpanel + g.po + (int64_t)g.k0 * m + g.k0;
+    const double* __restrict__ part = P.part + (int64_t)t.z * (SEL_KT * SEL_KT);
+#pragma unroll 4
+    for (int q = 0; q < SEL_KT * SEL_KT / 256; ++q) {
+        const int e = threadIdx.x + 256 * q;
+        const int i = row0 + (e & 63), j = col0 + (e >> 6);
+        if (i < g.nb && j <= i) {
+            double v = 0.0;
+            for (int c = 0; c < t.w; ++c) v += part[(int64_t)c * (SEL_KT * SEL_KT) + e];
+            zkk[(int64_t)j * m + i] = v;
+            zkk[(int64_t)i * m + j] = v;
+        }
+    }
+}
+
+// Z_II(c)[a, b] = Zfront_s[rel_c[a], rel_c[b]] for the children c of the fronts s of the
+// level just finished: a PUSH at the parent's level.  Z_II(c) lives in c's contribution-
+// block region of the work arena, which the memory plan keeps live over [level(c),
+// level(parent)] (sc_memory_plan_check) -- exactly from this write to the child's own
+// level, where it is read and c's children are served from it.  A child pulling at its
+// own level would find the parent's region recycled.
+__global__ __launch_bounds__(256) void sel_push_kernel(SelPlan P, const int4* __restrict__ tasks) {
+    const int4 t = tasks[blockIdx.x];
+    const int c = t.x, s = t.y;
+    const int mbc = P.sn_m[c] - (P.sn_start[c + 1] - P.sn_start[c]);
+    const int m = P.sn_m[s], w = P.sn_start[s + 1] - P.sn_start[s];
+    const int32_t* __restrict__ rel = P.relind + P.rel_ptr[c];
+    const double* __restrict__ zp = P.zpanel + P.panel_off[s];
+    const double* __restrict__ zi = P.zii + P.cb_off[s];
+    double* __restrict__ dst = P.zii + P.cb_off[c];
+    const int a = 64 * t.z + (threadIdx.x & 63);
+    if (a >= mbc) return;
+    const int pa = rel[a];
+#pragma unroll 4
+    for (int q = 0; q < 16; ++q) {
+        const int bb = 64 * t.w + (threadIdx.x >> 6) + 4 * q;
+        if (bb < mbc) {
+            const int pb = rel[bb];
+            dst[(int64_t)bb * mbc + a] = sel_zfront(zp, zi, m, w, max(pa, pb), min(pa, pb));
+        }
+    }
+}
+
+__global__ __launch_bounds__(LOGDET_NT) void sel_diag_kernel(SelPlan P, int ns, int n, const int32_t* __restrict__ post,
+                                                             double* __restrict__ diag) {
+    const int j = (int)blockIdx.x * LOGDET_NT + (int)threadIdx.x;
+    if (j >= n) return;
+    int lo = 0, hi = ns;  // sn_start[lo] <= j < sn_start[hi]
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (P.sn_start[mid] <= j)
+            lo = mid;
+        else
+            hi = mid;
+    }
+    diag[post[j]] = P.zpanel[P.panel_off[lo] + (int64_t)(j - P.sn_start[lo]) * (P.sn_m[lo] + 1)];
+}
+
+hipError_t launch_selinv_w(const SelPlan& P, const int2* tiles, int count, hipStream_t st) {
+    if (count <= 0) return hipSuccess;
+    hipLaunchKernelGGL(sel_w_kernel, dim3(count), dim3(64 * SEL_NW), 0, st, P, tiles);
+    return hipGetLastError();
+}
+
+hipError_t launch_selinv_zrk(const SelPlan& P, const int2* tiles, int count, hipStream_t st) {
+    if (count <= 0) return hipSuccess;
+    hipLaunchKernelGGL(sel_zrk_kernel, dim3(count), dim3(64 * SEL_NW), 0, st, P, tiles);
+    return hipGetLastError();
+}
+
+hipError_t launch_selinv_zkk(const SelPlan& P, const int4* tasks, int count, const int4* red, int nred,
+                             hipStream_t st) {
+    if (count > 0) hipLaunchKernelGGL(sel_zkk_kernel, dim3(count), dim3(256), 0, st, P, tasks);
+    if (nred > 0) hipLaunchKernelGGL(sel_zkk_reduce_kernel, dim3(nred), dim3(256), 0, st, P, red);
+    return hipGetLastError();
+}
+
+hipError_t launch_selinv_push(const SelPlan& P, const int4* tasks, int count, hipStream_t st) {
+    if (count <= 0) return hipSuccess;
+    hipLaunchKernelGGL(sel_push_kernel, dim3(count), dim3(256), 0, st, P, tasks);
+    return hipGetLastError();
+}
+
+hipError_t launch_selinv_diag(const SelPlan& P, int ns, int64_t n, const int32_t* post, double* diag, hipStream_t st) {
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(sel_diag_kernel, dim3((unsigned)((n + LOGDET_NT - 1) / LOGDET_NT)), dim3(LOGDET_NT), 0, st, P,
+                       ns, (int)n, post, diag);
+    return hipGetLastError();
+}
+
 }  // namespace sc

@@ -188,6 +188,53 @@ hipError_t launch_mul_lt_diag_multi(const SolvePlan& P, const int4* tasks, int c
 constexpr int LOGDET_NT = 256;
 hipError_t launch_logdet(const SolvePlan& P, int ns, int64_t n, double* part, double* out, hipStream_t st);
 
+// ---- selected inversion: Z = (P A P^T)^-1 on the pattern of L (Takahashi recurrence) ----
+// One 128-column block K = [k0, k1) of front s: R = front positions [k1, m), nr = m - k1;
+// W = L_RK X (nr x nb, column-major, ld = nr) sits at wbuf + woff for the length of its step.
+struct SelBlk {
+    int32_t s, k0;
+    int64_t woff;
+};
+struct SelPlan {
+    const int32_t* sn_start;
+    const int32_t* sn_m;
+    const int64_t* panel_off;  // per supernode, of both the L panel and the Z panel (m x w, ld = m)
+    const int64_t* cb_off;     // per supernode: Z_II (mb x mb, ld = mb, both triangles) in the work arena
+    const int64_t* rel_ptr;    // child c's contribution-block rows -> parent front positions
+    const int32_t* relind;
+    const double* lpanel;      // the factor, with the stored diagonal-block inverses (launch_solve_inv)
+    double* zpanel;            // Z panel: Z_JJ mirrored over the w x w pivot square, rows >= w below it
+    double* zii;               // the work arena
+    double* wbuf;
+    double* part;              // 64 x 64 partials of the split Z_KK products
+    const SelBlk* blk;
+};
+constexpr int SEL_NW = 4;             // waves of a W / Z_RK workgroup (8 = 128-row tiles measured 7 % slower at 128^3)
+constexpr int SEL_BM = 16 * SEL_NW;   // its output rows (16 per wave)
+constexpr int SEL_KT = 64;            // tile edge of the Z_KK products (four waves)
+constexpr int SEL_BK = 16;   // K staged per round through LDS
+// Z_KK products deeper than SEL_KSPLIT (K = nb + nr) are cut into chunks of SEL_KC, one
+// workgroup each: a tall front's block would otherwise run on three workgroups
+constexpr int SEL_KC = 256, SEL_KSPLIT = 512;
+inline int selinv_kchunks(int64_t K) { return K <= SEL_KSPLIT ? 1 : (int)((K + SEL_KC - 1) / SEL_KC); }
+// tiles (block, SEL_BM-row tile) of the nr x nb outputs, all nb columns per workgroup:
+// W = L_RK X with X = inv(L_KK) read in its stored form (X(i, k), k < i, at block row k,
+// column i; the diagonal as 1 / L(i, i)), then Z_RK = -Z_RR W on v_mfma_f64_16x16x4_f64 with
+// Z_RR read from the Z panel (pivot square, rows >= w straight and transposed) and Z_II;
+// Z_RK is also mirrored into the pivot square for rows < w.
+hipError_t launch_selinv_w(const SelPlan& P, const int2* tiles, int count, hipStream_t st);
+hipError_t launch_selinv_zrk(const SelPlan& P, const int2* tiles, int count, hipStream_t st);
+// Z_KK = X^T X - W^T Z_RK on the 64 x 64 tiles (ti, tj <= ti) of its lower triangle, each
+// written to both triangles of the block's square.  tasks (block, 2 ti + tj, chunk, slot):
+// slot < 0 the whole product; else one K chunk into partial slot `slot`, and red (block,
+// 2 ti + tj, first slot, chunks) sums a tile's partials in chunk order in a second launch.
+hipError_t launch_selinv_zkk(const SelPlan& P, const int4* tasks, int count, const int4* red, int nred,
+                             hipStream_t st);
+// tasks (child c, parent s, ti, tj): 64 x 64 tile of Z_II(c)[a, b] = Zfront_s[rel_c[a], rel_c[b]].
+hipError_t launch_selinv_push(const SelPlan& P, const int4* tasks, int count, hipStream_t st);
+// diag[post[j]] = Z panel diagonal of internal column j (addressing of launch_logdet)
+hipError_t launch_selinv_diag(const SelPlan& P, int ns, int64_t n, const int32_t* post, double* diag, hipStream_t st);
+
 // Small fronts (m <= maxm <= 128): one workgroup per front, factored in registers
 // (4 x 4 tiles per thread); seq: one workgroup runs the fronts in order (a whole
 // small tree in postorder, CBs through HBM).

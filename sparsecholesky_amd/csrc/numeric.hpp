@@ -358,6 +358,24 @@ struct Numeric {
     hipGraph_t apply_graph[2][APPLY_OPS] = {};
     hipGraphExec_t apply_gexec[2][APPLY_OPS] = {};
 
+    // selected inversion (selinv.cpp; single-device handles): the Z panel arena (gpanel's
+    // layout, allocated at the first call, kept), the W scratch of the largest step and the
+    // task lists, in execution order: levels down, 128-column steps down
+    struct SelStep {
+        int64_t toff, koff, roff, poff;  // first W / Z_RK tile, Z_KK task, Z_KK reduction, push task
+        int32_t tcount, kcount, rcount, pcount;  // pcount > 0 only after a level's last block (k0 = 0)
+    };
+    std::vector<SelStep> sel_steps;
+    bool sel_ready = false;
+    SelPlan SEL {};
+    int2* d_seltile = nullptr;
+    int4* d_selkk = nullptr;
+    int4* d_selred = nullptr;
+    int4* d_selpush = nullptr;
+    int64_t sel_gen = -1;              // factor_gen the Z panel belongs to
+    bool sel_profile = false;          // HIP events around every launch of the next calls
+    double sel_ms[4] = {0, 0, 0, 0};   // last profiled call: W, Z_RK, Z_KK, push (ms)
+
     std::string err;
 };
 
@@ -383,7 +401,9 @@ int64_t numeric_export(Numeric& N, int64_t* Lp, int32_t* Li, double* Lx);
 // Natural columns [j0, j1) in front-row form (count only when ri == NULL): column j
 // holds the rows of its supernode's front from its own position down (natural
 // numbering, front order; relaxed zeros included) with their values.  cp[j1-j0+1].
-int64_t numeric_export_cols(Numeric& N, int64_t j0, int64_t j1, int64_t* cp, int32_t* ri, double* rx);
+// pool: another arena in gpanel's layout to read the values from (the Z panel), or null.
+int64_t numeric_export_cols(Numeric& N, int64_t j0, int64_t j1, int64_t* cp, int32_t* ri, double* rx,
+                            const double* pool = nullptr);
 int64_t numeric_timing(Numeric& N, double* t, int nt);
 int64_t numeric_level_times(Numeric& N, double* ms, int nl);
 int64_t numeric_launch_trace(Numeric& N, int32_t* kind, int32_t* level, int32_t* strm, double* ms, double* flops,
@@ -418,6 +438,18 @@ int64_t numeric_apply_host_multi(Numeric& N, int32_t op, int32_t nrhs, const dou
                                  int64_t ldx);
 // log det A = 2 sum_j log L(j, j), reduced on the device in a fixed order.
 int64_t numeric_logdet(Numeric& N, double* logdet);
+// Selected inversion: Z = (P A P^T)^-1 on the pattern of L into the handle's Z panel
+// (synchronous).  Status rules of the solves; multi-rank and emulated handles:
+// SC_ERR_NOTIMPL.  The accessors compute first when the Z panel does not belong to the
+// current factorization: diag in A's own order, the export in numeric_export's layout.
+int64_t numeric_selinv(Numeric& N);
+int64_t numeric_selinv_diag_device(Numeric& N, double* d_d);
+int64_t numeric_selinv_diag_host(Numeric& N, double* d);
+int64_t numeric_selinv_export(Numeric& N, int64_t* Lp, int32_t* Li, double* Zx);
+// numeric_export_cols of the Z panel (for factors too large for numeric_selinv_export)
+int64_t numeric_selinv_export_cols(Numeric& N, int64_t j0, int64_t j1, int64_t* cp, int32_t* ri, double* rx);
+// Dense flops of the sweep from the symbolic structure (the formula of sc_selinv_flops).
+double selinv_flops(const Symbolic& S);
 // Destroys the captured solve and apply graphs (they point at one panel pool).
 void numeric_drop_solve_graphs(Numeric& N);
 int64_t debug_syrk(double* dC, int ldc, const double* dA, int lda, int M, int N, int K);

@@ -99,6 +99,13 @@ void set_pool_bases(Numeric& N, double* pbase, double* wbase);
 void finish_build(Numeric& N, SchedBuild& B, double* staging);
 SchedDigest schedule_digest(const Numeric& N, const SchedBuild& B);
 
+// solve.cpp
+// What every solve starts with: the whole factor in gpanel, the solve plan built.
+int64_t solve_prepare(Numeric& N);
+// The diagonal-block inverses of the current factorization in place (launch_solve_inv,
+// once per factorization; shared by the solves, the half solves and the selected inversion).
+int64_t solve_inverses(Numeric& N);
+
 // dist.cpp
 hipError_t comm_launch(Numeric& N, const Launch& L);
 int64_t dist_min_info(Numeric& N, int32_t& info);

@@ -38,7 +38,8 @@ int64_t numeric_export(Numeric& N, int64_t* Lp, int32_t* Li, double* Lx) {
     return st;
 }
 
-int64_t numeric_export_cols(Numeric& N, int64_t j0, int64_t j1, int64_t* cp, int32_t* ri, double* rx) {
+int64_t numeric_export_cols(Numeric& N, int64_t j0, int64_t j1, int64_t* cp, int32_t* ri, double* rx,
+                            const double* pool) {
     if (!N.factored) return SC_ERR_STATE;
     const int64_t st = numeric_status(N);
     if (st < 0) return st;
@@ -70,8 +71,8 @@ int64_t numeric_export_cols(Numeric& N, int64_t j0, int64_t j1, int64_t* cp, int
         base[s] = (int64_t)buf.size() - first;
         const size_t at = buf.size();
         buf.resize(at + (size_t)(last - first));
-        HIP_TRY(hipMemcpy(buf.data() + at, N.gpanel + N.gpo[s] + first, (size_t)(last - first) * sizeof(double),
-                          hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(buf.data() + at, (pool ? pool : N.gpanel) + N.gpo[s] + first,
+                          (size_t)(last - first) * sizeof(double), hipMemcpyDeviceToHost));
     }
     int64_t tot = 0;
     cp[0] = 0;
@@ -208,7 +209,7 @@ void numeric_drop_solve_graphs(Numeric& N) {
 
 // What both solves start with: the whole factor in gpanel (multi-rank: collective), the
 // plan built, and the captured sweeps dropped when they point at another panel pool.
-static int64_t solve_prepare(Numeric& N) {
+int64_t solve_prepare(Numeric& N) {
     HIP_TRY(hipSetDevice(N.device));
     TRY(numeric_gather(N));  // multi-rank: every rank solves with the whole factor
     if (N.solve_ready && N.SP.panel_pool != N.gpanel) {
@@ -430,7 +431,7 @@ static int64_t apply_run(Numeric& N, int family, int32_t op, F&& sweeps) {
 
 static bool apply_needs_inverses(int32_t op) { return op == SC_OP_SOLVE_L || op == SC_OP_SOLVE_LT; }
 
-static int64_t apply_inverses(Numeric& N) {
+int64_t solve_inverses(Numeric& N) {
     if (N.inv_gen != N.factor_gen) {  // shared with the solves
         HIP_TRY(launch_solve_inv(N.SP, N.d_sinv, N.n_sinv, N.d_sinv2, N.n_sinv2, N.stream));
         N.inv_gen = N.factor_gen;
@@ -505,7 +506,7 @@ static int64_t apply_multi(Numeric& N, int32_t op, int32_t nrhs, const double* B
         }
         return e;
     };
-    if (apply_needs_inverses(op)) TRY(apply_inverses(N));
+    if (apply_needs_inverses(op)) TRY(solve_inverses(N));
     const size_t colb = (size_t)n * sizeof(double);
     for (int32_t j0 = 0; j0 < nrhs; j0 += SOLVE_RHS) {
         const int nr = std::min<int32_t>(SOLVE_RHS, nrhs - j0);
@@ -577,7 +578,7 @@ int64_t numeric_apply_device(Numeric& N, int32_t op, const double* d_b, double* 
         }
         return e;
     };
-    if (apply_needs_inverses(op)) TRY(apply_inverses(N));
+    if (apply_needs_inverses(op)) TRY(solve_inverses(N));
     const size_t nb = (size_t)n * sizeof(double);
     if (d_b != io) HIP_TRY(hipMemcpyAsync(io, d_b, nb, hipMemcpyDeviceToDevice, s0));
     TRY(apply_run(N, 0, op, sweeps));
