@@ -191,8 +191,12 @@ int64_t sc_factor(sc_numeric* num, const double* Ax);
 /* Factor with device-resident values d_Ax (HBM).  Asynchronous on the library
  * stream unless sync != 0; sc_numeric_status() syncs and returns the status. */
 int64_t sc_factor_device(sc_numeric* num, const double* d_Ax, int32_t sync);
-/* Status of the last factorization: 0, or the 1-based natural column of the failing
- * pivot (not positive definite).  COLLECTIVE on a one-rank-per-process handle
+/* Status of the last factorization: 0, or the 1-based natural column of the first failing
+ * pivot (not positive definite): when several pivots fail, the smallest such column, which
+ * is what the reference's column-by-column chol() returns, on every kind of handle.  Under
+ * a fill-reducing ordering the column is counted in the order of P A P^T (column k there is
+ * column perm[k] of A, sc_symbolic_perm), the matrix that is factored: the reference's
+ * answer for P A P^T.  COLLECTIVE on a one-rank-per-process handle
  * (sc_numeric_create_dist / _dist_host): the first call after each factorization
  * reduces the minimum failing column over all ranks, so every rank must make it, in
  * the same order relative to the handle's other collective calls -- and so must

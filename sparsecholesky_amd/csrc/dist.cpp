@@ -552,7 +552,8 @@ hipError_t comm_launch(Numeric& N, const Launch& L) {
 }
 
 // Global status of a one-rank-per-process handle: the minimum failing column over
-// the ranks (each rank's info word holds its own fronts' failures only).
+// the ranks (each rank's info word holds its own fronts' failures only, as natural
+// columns, so the minimum is the reference's first failing column).
 int64_t dist_min_info(Numeric& N, int32_t& info) {
     if (N.xport) {
         std::vector<int32_t> got((size_t)N.nranks, info);

@@ -20,8 +20,13 @@ namespace sc {
 
 typedef double double4_t __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ void report_fail(int32_t* info, int32_t col_internal) {
-    atomicMin(info, col_internal + 1);
+// The status word holds the minimum failing NATURAL column + 1 (post: internal -> natural;
+// null in the debug harnesses, which number as they like).  Independent subtrees are
+// postordered in an order of the analysis' choosing, so the minimum internal column is not
+// the reference's first failing column; a front's own columns and its ancestors' have larger
+// natural indices than the column that failed first, so the minimum over every report is.
+__device__ __forceinline__ void report_fail(int32_t* info, const int32_t* post, int32_t col_internal) {
+    atomicMin(info, (post ? post[col_internal] : col_internal) + 1);
 }
 
 // g(k) of a child's compact block bounds (symbolic.cpp bounds()): [k_lo, k_hi, g(k_lo),
@@ -357,7 +362,7 @@ __device__ __forceinline__ void small_load(SmallRegs<KT>& R, const double* F, in
 // in column b take l_i in the pivot columns (and the update in any CB column).
 // colbuf: 2 x 4 * COLB doubles.
 template <int KT>
-__device__ __forceinline__ void small_steps(SmallRegs<KT>& R, double* colbuf, int w, int32_t* info, int c0) {
+__device__ __forceinline__ void small_steps(SmallRegs<KT>& R, double* colbuf, int w, int32_t* info, const int32_t* post, int c0) {
     for (int J = 0, b = 0; J < w; J += 4, ++b) {
         double* cb = colbuf + (b & 1) * 4 * COLB;
         const int nb = min(4, w - J);
@@ -389,7 +394,7 @@ __device__ __forceinline__ void small_steps(SmallRegs<KT>& R, double* colbuf, in
             double dd = D[c][c];
 #pragma unroll
             for (int t = 0; t < c; ++t) dd = fma(-Ld[c][t], Ld[c][t], dd);
-            if (c < nb && threadIdx.x == 0 && !(dd > 0.0)) report_fail(info, c0 + J + c);
+            if (c < nb && threadIdx.x == 0 && !(dd > 0.0)) report_fail(info, post, c0 + J + c);
             rc[c] = c < nb ? rsqrt_f64(dd) : 0.0;
             Ld[c][c] = dd * rc[c];
 #pragma unroll
@@ -448,7 +453,7 @@ __device__ __forceinline__ void small_steps(SmallRegs<KT>& R, double* colbuf, in
 // of the step -- the 4 x 4 block D and this tile's 4 column rows and 4 row rows -- is in
 // flight at once, before the serial L_D factorization; the pivot checks are folded into
 // one report per step.  Same arithmetic in the same order as small_steps (bitwise equal).
-__device__ __forceinline__ void small_steps1_fast(SmallRegs<1>& R, double* colbuf, int w, int32_t* info, int c0) {
+__device__ __forceinline__ void small_steps1_fast(SmallRegs<1>& R, double* colbuf, int w, int32_t* info, const int32_t* post, int c0) {
     const int bi = R.bi[0], bj = R.bj[0];
     for (int J = 0, b = 0; J < w; J += 4, ++b) {
         double* cb = colbuf + (b & 1) * 4 * COLB;
@@ -500,7 +505,7 @@ __device__ __forceinline__ void small_steps1_fast(SmallRegs<1>& R, double* colbu
                 Ld[r][c] = x * rc[c];
             }
         }
-        if (bad < 4 && threadIdx.x == 0) report_fail(info, c0 + J + bad);
+        if (bad < 4 && threadIdx.x == 0) report_fail(info, post, c0 + J + bad);
         if (!act) continue;
         auto solve = [&](const double2& x01, const double2& x23, double (&l)[4]) {
             const double cr[4] = {x01.x, x01.y, x23.x, x23.y};
@@ -685,7 +690,7 @@ __global__ __launch_bounds__(256) void front_small_kernel(DevPlan P, const int32
         small_tiles<KT>(R, m, w);
         small_assemble<KT == 1 ? 1 : 4>(P, s, c0, w, m, Ax, F);
         small_load<KT>(R, F, m);
-        small_steps<KT>(R, colbuf, w, P.info, c0);
+        small_steps<KT>(R, colbuf, w, P.info, P.post, c0);
         small_store_panel<KT>(R, P.panel_pool + P.panel_off[s], m, w);
         if (m > w) small_store_cb<KT>(R, P.cb_pool + P.cb_off[s], m, w);
         if (seq > 0) __syncthreads();  // global CB stores visible to the next front's loads
@@ -732,9 +737,9 @@ __global__ __launch_bounds__(256) void tiny_tree_kernel(DevPlan P, TinyPlan T, c
         small_tiles<1>(R, d.m, d.w);
         small_load<1>(R, Lm + d.img, d.m);
         if (SC_POTRF_FAST)
-            small_steps1_fast(R, colbuf, d.w, info, d.c0);
+            small_steps1_fast(R, colbuf, d.w, info, P.post, d.c0);
         else
-            small_steps<1>(R, colbuf, d.w, info, d.c0);
+            small_steps<1>(R, colbuf, d.w, info, P.post, d.c0);
         small_store_panel<1>(R, P.panel_pool + d.panel_off, d.m, d.w);
         if (d.m > d.w && R.bi[0] >= 0) {
             const int mb = d.m - d.w;
@@ -987,15 +992,42 @@ __global__ __launch_bounds__(64) void tiny_dense_kernel(DevPlan P, TinyPlan T, i
         if (o >= 0) P.panel_pool[o] = a[j];
 #endif
     }
+    // Not positive definite (rare, off the fast path): the status is the first failing column
+    // in NATURAL order.  The dense sweep above runs in postorder and a failed pivot's NaN
+    // spreads through the stored zeros into every later column, independent subtrees
+    // included, so `fail` is only the first in postorder.  A plain column sweep over the A
+    // values again, in which a failed pivot's column is dropped (l = 0) instead of
+    // poisoning the rest, sees every independent failure; failures it adds or misses in a
+    // failed column's ancestors have larger natural indices than that column.
+    int32_t nat = fail < n ? (P.post ? P.post[fail] : fail) : 0x7f7f7f7f;
+    if (fail < n) {  // wave-uniform
+        __shared__ double rec[NP * 64];  // column j at rec + 64 j, lane i = row i
+#pragma unroll
+        for (int j = 0; j < NP; ++j) {
+            const int2 q = T.a[j * 64 + i];
+            rec[j * 64 + i] = q.x >= 0 ? Ax[q.x] : 0.0;
+        }
+        for (int j = 0; j < n; ++j) {
+            wave_lds_sync();
+            const double d = rec[j * 64 + j];
+            const bool ok = d > 0.0;
+            if (!ok) nat = min(nat, P.post ? P.post[j] : j);
+            const double l = (ok && i > j) ? rec[j * 64 + i] / sqrt(d) : 0.0;
+            lv[i] = l;
+            wave_lds_sync();
+            for (int k = j + 1; k < n; ++k)
+                if (i >= k) rec[k * 64 + i] -= l * lv[k];
+        }
+    }
     // one wave: lane 0's system-scope release store below waits for the wave's panel
     // stores, so the status word is seen after the factor
     if (i == 0) {
         if (T.host_info) {  // the status word straight to the pinned host copy
-            const int32_t st = fail < n ? fail + 1 : 0x7f7f7f7f;
+            const int32_t st = fail < n ? nat + 1 : 0x7f7f7f7f;
             P.info[0] = st;
             __hip_atomic_store(T.host_info, st, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
         } else if (fail < n) {
-            report_fail(P.info, fail);
+            atomicMin(P.info, nat + 1);
         }
     }
 }
@@ -1110,7 +1142,7 @@ __global__ __launch_bounds__(CHAIN_NT) void front_chain_kernel(DevPlan P, ChainP
             if (i + 2 < count) prefetch(i + 2);
         }
         if (stamp && tid == 0) stamp[2] = __builtin_amdgcn_s_memtime();
-        small_steps<1>(R, colbuf, w, P.info, d.c0);
+        small_steps<1>(R, colbuf, w, P.info, P.post, d.c0);
         if (w == 0) lds_barrier();
         if (stamp && tid == 0) stamp[3] = __builtin_amdgcn_s_memtime();
         small_store_panel<1>(R, P.panel_pool + d.panel_off, m, w);
@@ -1164,9 +1196,9 @@ __global__ __launch_bounds__(256) void potrf_tiles_kernel(DevPlan P, const int2*
             R.v[0][r * 4 + c] = (R.bi[0] >= 0 && i < nb && i >= j) ? blk[(int64_t)j * m + i] : 0.0;
         }
     if (SC_POTRF_FAST)
-        small_steps1_fast(R, colbuf, nb, P.info, c0 + k0);
+        small_steps1_fast(R, colbuf, nb, P.info, P.post, c0 + k0);
     else
-        small_steps<1>(R, colbuf, nb, P.info, c0 + k0);
+        small_steps<1>(R, colbuf, nb, P.info, P.post, c0 + k0);
     if (R.bi[0] < 0) return;
 #pragma unroll
     for (int r = 0; r < 4; ++r)
@@ -1278,9 +1310,9 @@ __global__ __launch_bounds__(TRSM_ROWS) void trsm_panel_g_kernel(DevPlan P, cons
         return;
     }
     if (SC_POTRF_FAST)  // every block load has returned
-        small_steps1_fast(R, colbuf, PNB, P.info, c0 + k0);
+        small_steps1_fast(R, colbuf, PNB, P.info, P.post, c0 + k0);
     else
-        small_steps<1>(R, colbuf, PNB, P.info, c0 + k0);
+        small_steps<1>(R, colbuf, PNB, P.info, P.post, c0 + k0);
     if (R.bi[0] >= 0) {
 #pragma unroll
         for (int r = 0; r < 4; ++r)
@@ -1625,7 +1657,8 @@ __device__ __forceinline__ void mfma_kloop(const double* __restrict__ A, int64_t
 // (trsm_panel_g_kernel<2>): the 64-pivot POTRF leaves the chain's critical path and runs
 // beside the update's other tiles.  Same arithmetic in the same order: bitwise identical.
 template <int BK>
-__device__ __forceinline__ void panel_prefactor(const GemmTask& T, int32_t* info, double* smem) {
+__device__ __forceinline__ void panel_prefactor(const GemmTask& T, int32_t* info, const int32_t* post,
+                                                double* smem) {
     static_assert(2 * 2 * BK * (64 + 16) >= 64 * 65 / 2, "the packed diagonal block fits the operand LDS");
     double4_t acc[2][2];
 #pragma unroll
@@ -1662,7 +1695,7 @@ __device__ __forceinline__ void panel_prefactor(const GemmTask& T, int32_t* info
     small_tiles<1>(R, PNB, PNB);
     small_load<1>(R, F, PNB);
     __syncthreads();  // F is read: the column buffer overlays it
-    small_steps1_fast(R, smem, PNB, info, T.pf);
+    small_steps1_fast(R, smem, PNB, info, post, T.pf);
     if (R.bi[0] < 0) return;
 #pragma unroll
     for (int r = 0; r < 4; ++r)
@@ -1680,7 +1713,8 @@ __device__ __forceinline__ void panel_prefactor(const GemmTask& T, int32_t* info
 template <int BT, int WM, int WN, int TAG, int EPI, int LEAN = 0, int PF = 0>
 __device__ __forceinline__ void syrk_tile_body(const GemmTask* __restrict__ tasks, const int2* __restrict__ tiles,
                                                int bidx, const int64_t* __restrict__ gblk,
-                                               const GSeg* __restrict__ gseg, int32_t* info = nullptr) {
+                                               const GSeg* __restrict__ gseg, int32_t* info = nullptr,
+                                               const int32_t* post = nullptr) {
     constexpr int BK = LEAN ? 8 : 16;
     constexpr int LDT = BT + 16;
     constexpr int RTM = BT / WM / 16, RTN = BT / WN / 16;
@@ -1692,7 +1726,7 @@ __device__ __forceinline__ void syrk_tile_body(const GemmTask* __restrict__ task
     if constexpr (PF) {
         static_assert(BT == 64 && WM == 2 && WN == 2 && TAG == 0, "pre-factor on 64 x 64 panel-update tiles");
         if (tl.y < 0) {
-            panel_prefactor<BK>(T, info, smem);
+            panel_prefactor<BK>(T, info, post, smem);
             return;
         }
     }
@@ -1726,8 +1760,9 @@ template <int BT, int WM, int WN, int TAG, int EPI, int LEAN = 0, int PF = 0>
 __global__ __launch_bounds__(64 * WM * WN, LEAN ? (TAG ? 5 : 6) : 1) void syrk_mfma_kernel(const GemmTask* __restrict__ tasks,
                                                                   const int2* __restrict__ tiles,
                                                                   const int64_t* __restrict__ gblk,
-                                                                  const GSeg* __restrict__ gseg, int32_t* info) {
-    syrk_tile_body<BT, WM, WN, TAG, EPI, LEAN, PF>(tasks, tiles, blockIdx.x, gblk, gseg, info);
+                                                                  const GSeg* __restrict__ gseg, int32_t* info,
+                                                                  const int32_t* post) {
+    syrk_tile_body<BT, WM, WN, TAG, EPI, LEAN, PF>(tasks, tiles, blockIdx.x, gblk, gseg, info, post);
 }
 
 // ---------------------------------------------------------------------------
@@ -1805,13 +1840,13 @@ static void launch_syrk_t(const GemmTask* tasks, const int2* tiles, int n, int b
                           bool lean) {
     if (bt == 64 && lean)
         hipLaunchKernelGGL((syrk_mfma_kernel<64, 2, 2, TAG, EPI, 1>), dim3(n), dim3(256), 0, st, tasks, tiles, gt.blk,
-                           gt.seg, gt.info);
+                           gt.seg, gt.info, gt.post);
     else if (bt == 128)
         hipLaunchKernelGGL((syrk_mfma_kernel<128, 2, 4, TAG, EPI>), dim3(n), dim3(512), 0, st, tasks, tiles, gt.blk,
-                           gt.seg, gt.info);
+                           gt.seg, gt.info, gt.post);
     else
         hipLaunchKernelGGL((syrk_mfma_kernel<64, 2, 2, TAG, EPI>), dim3(n), dim3(256), 0, st, tasks, tiles, gt.blk,
-                           gt.seg, gt.info);
+                           gt.seg, gt.info, gt.post);
 }
 
 hipError_t launch_syrk(const GemmTask* tasks, const int2* tiles, int total_tiles, int bt, int tag, hipStream_t st,
@@ -1820,7 +1855,7 @@ hipError_t launch_syrk(const GemmTask* tasks, const int2* tiles, int total_tiles
     if (pf) {  // panel update with pre-factor workgroups: 64 x 64 tiles, batched epilogue
         if (bt != 64 || tag) return hipErrorInvalidValue;
         hipLaunchKernelGGL((syrk_mfma_kernel<64, 2, 2, 0, 1, 0, 1>), dim3(total_tiles), dim3(256), 0, st, tasks, tiles,
-                           gt.blk, gt.seg, gt.info);
+                           gt.blk, gt.seg, gt.info, gt.post);
         return hipGetLastError();
     }
     if (tag)

@@ -50,7 +50,8 @@ struct DevPlan {
     const int64_t* a_src;       // index into the input value array
     double* panel_pool;
     double* cb_pool;
-    int32_t* info;              // min failing internal column + 1
+    int32_t* info;              // min failing natural column + 1
+    const int32_t* post;        // n: internal -> natural column (what a failing pivot reports)
 };
 
 // One child's share of one 64 x 64 block (rb, cb) of a parent's contribution block
@@ -69,6 +70,7 @@ struct GatherTab {
     const int64_t* blk = nullptr;
     const GSeg* seg = nullptr;
     int32_t* info = nullptr;  // status word (pivot failures of the panel pre-factor workgroups)
+    const int32_t* post = nullptr;  // DevPlan.post
 };
 
 // One lower-trapezoid SYRK update: C[i,j] -= sum_k A[i,k] A[j,k], j < N, j <= i < M.

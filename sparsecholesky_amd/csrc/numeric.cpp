@@ -183,6 +183,9 @@ int64_t numeric_init(Numeric& N, const Symbolic& S, int device) {
     if ((rc = dalloc(N, 64, p))) return rc;
     N.d_info = (int32_t*)p;
     P0.info = N.d_info;
+    int32_t* d_post = nullptr;
+    if ((rc = upload(N, S.post, d_post))) return rc;
+    P0.post = d_post;
     if (hipHostMalloc((void**)&N.h_info, sizeof(int32_t) * 16, hipHostMallocMapped | hipHostMallocCoherent) !=
         hipSuccess) {
         N.err = "hipHostMalloc failed";
@@ -337,6 +340,7 @@ static hipError_t launch_one(Numeric& N, const Launch& L, const double* d_Ax) {
         {
             GatherTab gt = N.gtab;
             gt.info = N.d_info;
+            gt.post = P.post;
             return launch_syrk(N.d_gemm + L.off, N.d_tiles + L.toff, L.count, L.bt, c == C_SYRK_CB ? 1 : 0, st, L.epi,
                                gt, L.lean != 0, L.pf != 0);
         }
@@ -472,10 +476,12 @@ int64_t numeric_status(Numeric& N) {
         const int64_t rc = dist_min_info(N, info);
         if (rc != SC_OK) return rc;
     }
+    // the word is already the minimum failing natural column + 1 (report_fail): the minimum
+    // over the kernels' reports, and over the ranks, is the reference's first failing column
     if (info == 0x7f7f7f7f || info <= 0)
         N.status = 0;
     else
-        N.status = (int64_t)N.S->post[info - 1] + 1;
+        N.status = (int64_t)info;
     N.status_valid = true;
     if (N.profile == 1) {
         std::memset(N.phase_ms, 0, sizeof(N.phase_ms));
