@@ -24,6 +24,20 @@ extern "C" {
  * pointers, column-major) through the fp64 MFMA SYRK kernel. */
 int64_t sc_debug_syrk(double* dC, int32_t ldc, const double* dA, int32_t lda, int32_t M, int32_t N,
                       int32_t K);
+/* sc_debug_syrk on the kernel instance the caller names: bt = 64 or 128 (tile edge), lean
+ * = 1 only with bt = 64, tag and epi 0 or 1.  Never gathers, never pre-factors.  Needs 1 <=
+ * N <= M, K >= 1, lda and ldc >= M; an inconsistent combination returns SC_ERR_ARG before
+ * any device call.  sc_debug_syrk is bt = 64, lean = (K <= 128), tag = epi = 0. */
+int64_t sc_debug_syrk_ex(double* dC, int32_t ldc, const double* dA, int32_t lda, int32_t M, int32_t N, int32_t K,
+                         int32_t bt, int32_t lean, int32_t tag, int32_t epi);
+/* The panel kernels on block k0 (a multiple of 64, nb = min(64, w - k0) columns) of a
+ * caller's m x w front panel (device, column-major, ld = m, 1 <= w <= m), through a
+ * one-front plan with an identity post table.  mode 0: the diagonal-block POTRF alone; 1:
+ * the TRSM with the POTRF fused; 2: the POTRF, then the TRSM on the factored block; 3: the
+ * POTRF, then the partial-block TRSM.  Modes 1 and 2 need nb = 64, mode 3 nb < 64;
+ * anything else returns SC_ERR_ARG before any device call.  *info receives the status
+ * word: 0, or the first failing column of the panel + 1. */
+int64_t sc_debug_panel(double* dF, int32_t m, int32_t w, int32_t k0, int32_t mode, int32_t* info);
 /* Best wall time (ms) of reps synchronous factorizations from device values
  * (sc_factor_device(num, d_Ax, 1): launch, run, status read-back), timed in C. */
 int64_t sc_debug_time_factor(sc_numeric* num, const double* d_Ax, int32_t reps, double* best_ms);
@@ -72,6 +86,12 @@ int64_t sc_debug_contention(int32_t M, int32_t K, int32_t chain_rows, int32_t nc
  * messages and gather segments.  Writes at most cap values, returns their number. */
 int64_t sc_debug_schedule_digest(const sc_symbolic* sym, int32_t nranks, int32_t rank, int32_t emulate,
                                  int64_t* out, int64_t cap);
+/* The SYRK launches of the schedule sc_debug_schedule_digest plans (same arguments), in
+ * schedule order, eight values each: kind (0 panel update, 1 contribution block), tile
+ * edge bt, lean, epi, pf, tail, tile count, and whether any task of the launch gathers
+ * its children (gs >= 0).  Writes at most cap values, returns their number. */
+int64_t sc_debug_schedule_syrk(const sc_symbolic* sym, int32_t nranks, int32_t rank, int32_t emulate,
+                               int64_t* out, int64_t cap);
 /* The same digest of a live handle, hashed at creation from what it uploaded. */
 int64_t sc_debug_numeric_digest(const sc_numeric* num, int64_t* out, int64_t cap);
 

@@ -166,6 +166,8 @@ _SIGS = [
     ("sc_memory_plan", _I64, [_P, _I32, _P, _P, _P]),
     ("sc_memory_plan_check", _I64, [_P, _I32]),
     ("sc_debug_syrk", _I64, [_P, _I32, _P, _I32, _I32, _I32, _I32]),
+    ("sc_debug_syrk_ex", _I64, [_P, _I32, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32]),
+    ("sc_debug_panel", _I64, [_P, _I32, _I32, _I32, _I32, C.POINTER(_I32)]),
     ("sc_debug_bench", _I64, [_I32, _I32, _I32, _I32, _I32, C.POINTER(_D)]),
     ("sc_device_count", _I64, []),
     ("sc_debug_chain_stamps", _I64, [_P, _I32, _P, _I64]),
@@ -176,6 +178,7 @@ _SIGS = [
     ("sc_debug_hwid", _I64, [_I32, _I32, _I32, _P]),
     ("sc_debug_contention", _I64, [_I32, _I32, _I32, _I32, _I32, _I32, _P]),
     ("sc_debug_schedule_digest", _I64, [_P, _I32, _I32, _I32, _P, _I64]),
+    ("sc_debug_schedule_syrk", _I64, [_P, _I32, _I32, _I32, _P, _I64]),
     ("sc_debug_numeric_digest", _I64, [_P, _P, _I64]),
 ]
 
@@ -575,6 +578,19 @@ class Symbolic:
         rank, 1 every rank in this process (``virtual=True``), 2 the same with ``rccl_self=True``."""
         return _digest_dict(lambda out, n: lib().sc_debug_schedule_digest(self.h, nranks, rank, emulate, out, n),
                             "schedule_digest")
+
+    def syrk_launches(self, nranks: int = 1, rank: int = 0, emulate: int = 0):
+        """The SYRK launches of the schedule :meth:`schedule_digest` plans (same arguments), in
+        schedule order: one dict per launch with ``kind`` ("panel" or "cb"), ``bt``, ``lean``,
+        ``epi``, ``pf``, ``tail``, ``tiles`` and ``gather`` (any task gathers its children)."""
+        n = _check(lib().sc_debug_schedule_syrk(self.h, nranks, rank, emulate, None, 0), "syrk_launches")
+        v = np.zeros(max(n, 1), dtype=np.int64)
+        assert _check(lib().sc_debug_schedule_syrk(self.h, nranks, rank, emulate, _ptr(v), n), "syrk_launches") == n
+        keys = ("kind", "bt", "lean", "epi", "pf", "tail", "tiles", "gather")
+        out = [dict(zip(keys, row)) for row in v[:n].reshape(-1, 8).tolist()]
+        for d in out:
+            d["kind"] = "cb" if d["kind"] else "panel"
+        return out
 
     def dist_steps(self, nranks: int) -> dict:
         """The plan's comm steps in order: kind (0 INIT, 1 SLAB, 2 DELIVER), level, front,

@@ -377,6 +377,16 @@ int64_t sc_debug_schedule_digest(const sc_symbolic* sym, int32_t nranks, int32_t
     return rc != SC_OK ? rc : digest_out(d, out, cap);
 }
 
+int64_t sc_debug_schedule_syrk(const sc_symbolic* sym, int32_t nranks, int32_t rank, int32_t emulate, int64_t* out,
+                               int64_t cap) {
+    if (!sym || cap < 0 || (cap > 0 && !out)) return SC_ERR_ARG;
+    std::vector<int64_t> v;
+    const int64_t rc = sc::schedule_syrk_host(sym->S, nranks, rank, emulate, v, g_last_error);
+    if (rc != SC_OK) return rc;
+    if (out) std::copy(v.begin(), v.begin() + std::min<int64_t>(cap, (int64_t)v.size()), out);
+    return (int64_t)v.size();
+}
+
 int64_t sc_debug_numeric_digest(const sc_numeric* num, int64_t* out, int64_t cap) {
     if (!num || !num->N || cap < 0) return SC_ERR_ARG;
     return digest_out(num->N->digest, out, cap);
@@ -799,6 +809,17 @@ int64_t sc_debug_syrk(double* dC, int32_t ldc, const double* dA, int32_t lda, in
                       int32_t K) {
     if (!dC || !dA || M < 0 || N < 0 || K < 0 || N > M) return SC_ERR_ARG;
     return sc::debug_syrk(dC, ldc, dA, lda, M, N, K);
+}
+
+int64_t sc_debug_syrk_ex(double* dC, int32_t ldc, const double* dA, int32_t lda, int32_t M, int32_t N, int32_t K,
+                         int32_t bt, int32_t lean, int32_t tag, int32_t epi) {
+    if (!dC || !dA) return SC_ERR_ARG;
+    return sc::debug_syrk_ex(dC, ldc, dA, lda, M, N, K, bt, lean, tag, epi);
+}
+
+int64_t sc_debug_panel(double* dF, int32_t m, int32_t w, int32_t k0, int32_t mode, int32_t* info) {
+    if (!dF || !info) return SC_ERR_ARG;
+    return sc::debug_panel(dF, m, w, k0, mode, info);
 }
 
 int64_t sc_debug_bench(int32_t which, int32_t M, int32_t K, int32_t reps, int32_t arg, double* tflops) {

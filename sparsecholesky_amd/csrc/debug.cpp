@@ -1,10 +1,20 @@
-// Debug and microbenchmark hooks (sc_debug_syrk, sc_debug_bench): the SYRK kernel on
-// caller data, kernel ceilings on synthetic operands.
+// Debug and microbenchmark hooks (sc_debug_syrk, sc_debug_syrk_ex, sc_debug_panel,
+// sc_debug_bench): the SYRK and panel kernels on caller data, kernel ceilings on synthetic
+// operands.
 #include "numeric_impl.hpp"
 
 namespace sc {
 
-int64_t debug_syrk(double* dC, int ldc, const double* dA, int lda, int M, int Nn, int K) {
+int64_t debug_syrk_ex(double* dC, int ldc, const double* dA, int lda, int M, int Nn, int K, int bt, int lean, int tag,
+                      int epi) {
+    // every combination launch_syrk could not run as asked, and sizes whose byte offsets
+    // would leave the kernels' 32-bit buffer ranges, are refused before any HIP call
+    constexpr int LD_MAX = 1 << 21;
+    if (!dC || !dA || M < 1 || Nn < 1 || Nn > M || K < 1 || lda < M || ldc < M || lda > LD_MAX || ldc > LD_MAX)
+        return SC_ERR_ARG;
+    if ((bt != SYRK_BT_SMALL && bt != SYRK_BT_LARGE) || (lean != 0 && lean != 1) || (lean && bt != SYRK_BT_SMALL) ||
+        (tag != 0 && tag != 1) || (epi != 0 && epi != 1))
+        return SC_ERR_ARG;
     GemmTask t {};
     t.C = dC;
     t.A = dA;
@@ -13,7 +23,6 @@ int64_t debug_syrk(double* dC, int ldc, const double* dA, int lda, int M, int Nn
     t.M = M;
     t.N = Nn;
     t.K = K;
-    const int bt = SYRK_BT_SMALL;
     std::vector<int2> tiles;
     append_tiles(tiles, 0, M, Nn, bt);
     xcd_order(tiles.data(), (int64_t)tiles.size());
@@ -27,12 +36,105 @@ int64_t debug_syrk(double* dC, int ldc, const double* dA, int lda, int M, int Nn
     hipError_t e = hipMemcpy(d, &t, sizeof(t), hipMemcpyHostToDevice);
     if (e == hipSuccess && !tiles.empty())
         e = hipMemcpy(dt, tiles.data(), tiles.size() * sizeof(int2), hipMemcpyHostToDevice);
-    // K <= 128: the lean instance (as the schedule's default syrk_lean_kmax picks it)
-    if (e == hipSuccess) e = launch_syrk(d, dt, (int)tiles.size(), bt, 0, nullptr, 0, GatherTab {}, K <= 128);
+    if (e == hipSuccess) e = launch_syrk(d, dt, (int)tiles.size(), bt, tag, nullptr, epi, GatherTab {}, lean != 0);
     hipError_t e2 = hipDeviceSynchronize();
     (void)hipFree(d);
     (void)hipFree(dt);
     return (e == hipSuccess && e2 == hipSuccess) ? SC_OK : SC_ERR_HIP;
+}
+
+int64_t debug_syrk(double* dC, int ldc, const double* dA, int lda, int M, int Nn, int K) {
+    if (M == 0 || Nn == 0 || K == 0) return SC_OK;  // an empty update
+    // K <= 128: the lean instance (as the schedule's default syrk_lean_kmax picks it)
+    return debug_syrk_ex(dC, ldc, dA, lda, M, Nn, K, SYRK_BT_SMALL, K <= 128, 0, 0);
+}
+
+namespace {
+
+// One front (m rows, w columns, internal columns 0 .. w - 1) as a device plan over a
+// caller's panel pool, with the task arrays of one 64-column step: what the panel
+// microbenchmark and the panel debug hook share.
+struct PanelRig {
+    void *d_s = nullptr, *d_m = nullptr, *d_o = nullptr, *d_info = nullptr, *d_pt = nullptr, *d_tr = nullptr,
+         *d_arr = nullptr, *d_post = nullptr;
+    DevPlan P {};
+    int nt = 0;
+    // tr: the step's TRSM tasks; identity_post: failing pivots report through a post table
+    // (internal = natural) as in a factorization, else through none (the harness numbering)
+    int64_t init(double* pool, int m, int w, int k0, const std::vector<TrsmTask>& tr, bool identity_post) {
+        const int32_t hs[2] = {0, w}, hm[1] = {m};
+        const int64_t ho[2] = {0, (int64_t)m * w};
+        const int2 pt = make_int2(0, k0);
+        nt = (int)tr.size();
+        if (hipMalloc(&d_s, 8) || hipMalloc(&d_m, 4) || hipMalloc(&d_o, 16) || hipMalloc(&d_info, 4) ||
+            hipMalloc(&d_pt, 8) || hipMalloc(&d_tr, std::max<size_t>(1, tr.size()) * sizeof(TrsmTask)) ||
+            hipMalloc(&d_arr, 4) || (identity_post && hipMalloc(&d_post, (size_t)w * 4)))
+            return SC_ERR_DEVMEM;
+        if (hipMemset(d_arr, 0, 4) || hipMemset(d_info, 0, 4) || hipMemcpy(d_s, hs, 8, hipMemcpyHostToDevice) ||
+            hipMemcpy(d_m, hm, 4, hipMemcpyHostToDevice) || hipMemcpy(d_o, ho, 16, hipMemcpyHostToDevice) ||
+            hipMemcpy(d_pt, &pt, 8, hipMemcpyHostToDevice))
+            return SC_ERR_HIP;
+        if (!tr.empty() && hipMemcpy(d_tr, tr.data(), tr.size() * sizeof(TrsmTask), hipMemcpyHostToDevice))
+            return SC_ERR_HIP;
+        if (identity_post) {
+            std::vector<int32_t> id((size_t)w);
+            for (int j = 0; j < w; ++j) id[(size_t)j] = j;
+            if (hipMemcpy(d_post, id.data(), id.size() * 4, hipMemcpyHostToDevice)) return SC_ERR_HIP;
+        }
+        P.sn_start = (const int32_t*)d_s;
+        P.sn_m = (const int32_t*)d_m;
+        P.panel_off = (const int64_t*)d_o;
+        P.info = (int32_t*)d_info;
+        P.post = (const int32_t*)d_post;
+        P.panel_pool = pool;
+        return SC_OK;
+    }
+    hipError_t potrf() const { return launch_potrf_diag(P, (const int2*)d_pt, 1, nullptr); }
+    hipError_t trsm(bool partial, int pre) const {
+        return launch_trsm_panel(P, (const TrsmTask*)d_tr, nt, nullptr, partial, (int32_t*)d_arr, pre);
+    }
+    ~PanelRig() {
+        for (void* p : {d_s, d_m, d_o, d_info, d_pt, d_tr, d_arr, d_post})
+            if (p) (void)hipFree(p);
+    }
+};
+
+}  // namespace
+
+int64_t debug_panel(double* dF, int m, int w, int k0, int mode, int32_t* info) {
+    // m * 64 * 8 bytes is the TRSM kernels' buffer range (32 bits)
+    if (!dF || !info || m < 1 || m > (1 << 22) || w < 1 || w > m || k0 < 0 || k0 >= w || k0 % PNB != 0 || mode < 0 ||
+        mode > 3)
+        return SC_ERR_ARG;
+    const int nb = std::min(PNB, w - k0), k1 = k0 + nb;
+    if ((mode == 1 || mode == 2) && nb != PNB) return SC_ERR_ARG;  // the full-block TRSM kernels
+    if (mode == 3 && nb == PNB) return SC_ERR_ARG;                 // the partial-block TRSM kernel
+    // the step's tasks as the schedule cuts them (ScheduleBuilder::trsm_tasks): TRSM_ROWS
+    // rows each from row k1 down; the fused instance keeps one task for a block with no rows
+    std::vector<TrsmTask> tr;
+    const int ctr = mode == 1 ? 1 : 0;
+    if (mode != 0)
+        for (int r0 = k1; r0 < (ctr ? std::max(m, k1 + 1) : m); r0 += TRSM_ROWS) tr.push_back(TrsmTask {0, k0, r0, m, ctr});
+    PanelRig rig;
+    int64_t rc = rig.init(dF, m, w, k0, tr, true);
+    // the status word armed as a factorization arms it (failing pivots report by atomicMin)
+    constexpr int32_t ARMED = 0x7f7f7f7f;
+    if (rc == SC_OK && hipMemset(rig.d_info, 0x7f, sizeof(int32_t)) != hipSuccess) rc = SC_ERR_HIP;
+    if (rc == SC_OK) {
+        hipError_t e = hipSuccess;
+        if (mode != 1) e = rig.potrf();
+        if (e == hipSuccess && mode == 1) e = rig.trsm(false, 0);
+        if (e == hipSuccess && mode == 2) e = rig.trsm(false, 2);
+        if (e == hipSuccess && mode == 3) e = rig.trsm(true, 0);
+        const hipError_t e2 = hipDeviceSynchronize();
+        int32_t st = 0;
+        const hipError_t e3 = e2 == hipSuccess ? hipMemcpy(&st, rig.d_info, 4, hipMemcpyDeviceToHost) : e2;
+        if (e != hipSuccess || e2 != hipSuccess || e3 != hipSuccess)
+            rc = SC_ERR_HIP;
+        else
+            *info = (st == ARMED || st <= 0) ? 0 : st;
+    }
+    return rc;
 }
 
 // Panel-kernel microbenchmarks on one synthetic front (m = M rows, w = 64):
@@ -51,47 +153,27 @@ static int64_t bench_panel(int which, int M, int reps, double* out) {
     };
     for (int j = 0; j < w; ++j)
         for (int i = 0; i < M; ++i) h[(size_t)j * M + i] = (i == j) ? 64.0 : rnd();
-    int32_t hs[2] = {0, w}, hm[1] = {M};
-    int64_t ho[2] = {0, (int64_t)nel};
     std::vector<TrsmTask> tr;
     for (int r0 = w; r0 < M; r0 += TRSM_ROWS) tr.push_back(TrsmTask {0, 0, r0, M, 1});
-    int2 pt = make_int2(0, 0);
-    void *d_pan = nullptr, *d_ref = nullptr, *d_s = nullptr, *d_m = nullptr, *d_o = nullptr, *d_info = nullptr,
-         *d_pt = nullptr, *d_tr = nullptr, *d_arr = nullptr;
+    void *d_pan = nullptr, *d_ref = nullptr;
     const size_t bytes = (nel + PNB) * sizeof(double);
     int64_t rc = SC_OK;
     hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (hipMalloc(&d_pan, bytes) || hipMalloc(&d_ref, bytes) || hipMalloc(&d_s, 8) || hipMalloc(&d_m, 4) ||
-        hipMalloc(&d_o, 16) || hipMalloc(&d_info, 4) || hipMalloc(&d_pt, 8) ||
-        hipMalloc(&d_tr, std::max<size_t>(1, tr.size()) * sizeof(TrsmTask)) || hipMalloc(&d_arr, 4) ||
-        hipMemset(d_arr, 0, 4) || hipEventCreate(&e0) ||
-        hipEventCreate(&e1)) {
+    PanelRig rig;
+    if (hipMalloc(&d_pan, bytes) || hipMalloc(&d_ref, bytes) || hipEventCreate(&e0) || hipEventCreate(&e1)) {
         rc = SC_ERR_DEVMEM;
-    } else {
+    } else if ((rc = rig.init((double*)d_pan, M, w, 0, tr, false)) == SC_OK) {
         (void)hipMemcpy(d_ref, h.data(), bytes, hipMemcpyHostToDevice);
-        (void)hipMemcpy(d_s, hs, 8, hipMemcpyHostToDevice);
-        (void)hipMemcpy(d_m, hm, 4, hipMemcpyHostToDevice);
-        (void)hipMemcpy(d_o, ho, 16, hipMemcpyHostToDevice);
-        (void)hipMemset(d_info, 0, 4);
-        (void)hipMemcpy(d_pt, &pt, 8, hipMemcpyHostToDevice);
-        if (!tr.empty()) (void)hipMemcpy(d_tr, tr.data(), tr.size() * sizeof(TrsmTask), hipMemcpyHostToDevice);
-        DevPlan P {};
-        P.sn_start = (const int32_t*)d_s;
-        P.sn_m = (const int32_t*)d_m;
-        P.panel_off = (const int64_t*)d_o;
-        P.info = (int32_t*)d_info;
-        P.panel_pool = (double*)d_pan;
-        const int nt = (int)tr.size();
         (void)hipMemcpy(d_pan, d_ref, bytes, hipMemcpyDeviceToDevice);
-        (void)launch_potrf_diag(P, (const int2*)d_pt, 1, nullptr);
+        (void)rig.potrf();
         double tot = 0.0;
         for (int r = 0; r < reps + 1; ++r) {
             if (which == 2) (void)hipMemcpy(d_pan, d_ref, bytes, hipMemcpyDeviceToDevice);
             (void)hipEventRecord(e0, nullptr);
             if (which == 2)
-                (void)launch_potrf_diag(P, (const int2*)d_pt, 1, nullptr);
+                (void)rig.potrf();
             else
-                (void)launch_trsm_panel(P, (const TrsmTask*)d_tr, nt, nullptr, false, (int32_t*)d_arr);
+                (void)rig.trsm(false, 0);
             (void)hipEventRecord(e1, nullptr);
             (void)hipEventSynchronize(e1);
             float ms = 0.f;
@@ -101,7 +183,7 @@ static int64_t bench_panel(int which, int M, int reps, double* out) {
         *out = 1e3 * tot / reps;
         if (hipGetLastError() != hipSuccess) rc = SC_ERR_HIP;
     }
-    for (void* p : {d_pan, d_ref, d_s, d_m, d_o, d_info, d_pt, d_tr, d_arr})
+    for (void* p : {d_pan, d_ref})
         if (p) (void)hipFree(p);
     if (e0) (void)hipEventDestroy(e0);
     if (e1) (void)hipEventDestroy(e1);

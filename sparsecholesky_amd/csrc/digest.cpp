@@ -219,10 +219,12 @@ SchedDigest schedule_digest(const Numeric& N, const SchedBuild& B) {
     return D;
 }
 
-int64_t schedule_digest_host(const Symbolic& S, int nranks, int rank, int emulate, SchedDigest& out,
-                             std::string& err) {
+namespace {
+
+// The schedule of a handle planned on the host (placeholder pool bases): N.sched and B.
+int64_t plan_schedule_host(const Symbolic& S, int nranks, int rank, int emulate, Numeric& N, SchedBuild& B,
+                           std::string& err) {
     if (nranks < 1 || rank < 0 || rank >= nranks || emulate < 0 || emulate > 2) return SC_ERR_ARG;
-    Numeric N;
     N.rank = emulate ? 0 : rank;
     N.nranks = nranks;
     N.emulated = emulate != 0;
@@ -234,7 +236,6 @@ int64_t schedule_digest_host(const Symbolic& S, int nranks, int rank, int emulat
     }
     // pool bases that are never dereferenced, far enough apart that no offset crosses
     auto base = [](int arena) { return (uintptr_t)arena << 44; };
-    SchedBuild B;
     if ((rc = numeric_plan_host(N, S)) == SC_OK) {
         for (RankMem& R : N.R) R.P.relind = (const int32_t*)base(A_RELIND);
         set_pool_bases(N, (double*)base(A_PANEL), (double*)base(A_WORK));
@@ -245,7 +246,35 @@ int64_t schedule_digest_host(const Symbolic& S, int nranks, int rank, int emulat
         return rc;
     }
     finish_build(N, B, (double*)base(A_STAGING));
+    return SC_OK;
+}
+
+}  // namespace
+
+int64_t schedule_digest_host(const Symbolic& S, int nranks, int rank, int emulate, SchedDigest& out,
+                             std::string& err) {
+    Numeric N;
+    SchedBuild B;
+    const int64_t rc = plan_schedule_host(S, nranks, rank, emulate, N, B, err);
+    if (rc != SC_OK) return rc;
     out = schedule_digest(N, B);
+    return SC_OK;
+}
+
+int64_t schedule_syrk_host(const Symbolic& S, int nranks, int rank, int emulate, std::vector<int64_t>& out,
+                           std::string& err) {
+    Numeric N;
+    SchedBuild B;
+    const int64_t rc = plan_schedule_host(S, nranks, rank, emulate, N, B, err);
+    if (rc != SC_OK) return rc;
+    out.clear();
+    for (const Launch& L : N.sched) {
+        if (L.kind != L_PANEL && L.kind != L_CB) continue;
+        int64_t gathers = 0;
+        for (int64_t q = L.off; q < L.off + L.ntasks; ++q) gathers |= B.gemm[(size_t)q].gs >= 0;
+        const int64_t v[8] = {L.kind == L_CB, L.bt, L.lean, L.epi, L.pf, L.tail, L.count, gathers};
+        out.insert(out.end(), v, v + 8);
+    }
     return SC_OK;
 }
 

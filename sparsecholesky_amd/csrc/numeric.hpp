@@ -390,6 +390,10 @@ int64_t numeric_init(Numeric& N, const Symbolic& S, int device);
 // would build, planned on the host with placeholder pool bases.  No HIP call.
 int64_t schedule_digest_host(const Symbolic& S, int nranks, int rank, int emulate, SchedDigest& out,
                              std::string& err);
+// The SYRK launches of the same host-planned schedule, in schedule order, eight values
+// each: kind (0 panel, 1 CB), bt, lean, epi, pf, tail, tiles, any task gathers (gs >= 0).
+int64_t schedule_syrk_host(const Symbolic& S, int nranks, int rank, int emulate, std::vector<int64_t>& out,
+                           std::string& err);
 
 int64_t numeric_create(const Symbolic& S, int device, Numeric*& out, std::string& err);
 int64_t numeric_factor(Numeric& N, const double* d_Ax, bool sync);
@@ -453,6 +457,15 @@ double selinv_flops(const Symbolic& S);
 // Destroys the captured solve and apply graphs (they point at one panel pool).
 void numeric_drop_solve_graphs(Numeric& N);
 int64_t debug_syrk(double* dC, int ldc, const double* dA, int lda, int M, int N, int K);
+// debug_syrk on the instance the caller names: bt 64 / 128, lean (64 only), tag, epi; no
+// gather, no pre-factor.  SC_ERR_ARG on an inconsistent combination, before any HIP call.
+int64_t debug_syrk_ex(double* dC, int ldc, const double* dA, int lda, int M, int N, int K, int bt, int lean, int tag,
+                      int epi);
+// The panel kernels on block k0 of a caller's m x w front panel (device, column-major, ld =
+// m) through a one-front plan with an identity post table; mode 0 POTRF alone, 1 the fused
+// TRSM, 2 POTRF then the prefactored TRSM, 3 (partial blocks) POTRF then the partial TRSM.
+// *info: the status word (first failing column + 1, or 0).
+int64_t debug_panel(double* dF, int m, int w, int k0, int mode, int32_t* info);
 int64_t numeric_chain_stamps(Numeric& N, int enable, uint64_t* out, int64_t cap);
 int64_t debug_bench(int which, int M, int K, int reps, int arg, double* tflops);
 int64_t debug_contention(int M, int K, int chain_rows, int nchain, int mode, int mask_stride, double* out);

@@ -1,7 +1,9 @@
 """Host tests of the prescribed-tree catalogue (tests/zoo.py): the generator against the
 analysis, every case against the code path it is named for (read off the host schedule digest
 and the supernode partition), multi-rank plans, the oracle against the long-double factor, and
-the expected status of inputs with two failing pivots.  No GPU."""
+the expected status of inputs with two failing pivots; for the big_ cases the SYRK kernel
+instance every case and tag reaches (Symbolic.syrk_launches), and the argument checks of the
+kernel debug hooks.  No GPU."""
 import numpy as np
 import pytest
 
@@ -160,9 +162,163 @@ def test_block_edges_and_forest():
     assert st.w[0] == 1 and st.w[-1] == 1 and st.parent[-1] < 0  # isolated columns first and last
 
 
+# ---- 2b. the big_ cases: which SYRK instance each case and tag reaches ----
+def _launches(name, tag):
+    """(symbolic, {(kind, bt, lean, epi, pf, gather): [tile counts]}, calls) of a case's host schedule under a tag."""
+    symb = sc.Symbolic(zoo.case(name).A, **zoo.OPTS[tag])
+    inst = {}
+    for l in symb.syrk_launches():
+        inst.setdefault((l["kind"], l["bt"], l["lean"], l["epi"], l["pf"], l["gather"]), []).append(l["tiles"])
+        assert l["tail"] == 0  # see test_big_cases_cover_every_syrk_instance
+    return symb, inst, symb.schedule_digest()["calls"]
+
+
+CB128_G1, CB128_G0 = ("cb", 128, 0, 1, 0, 1), ("cb", 128, 0, 0, 0, 1)  # 128-tile gather: short K (epi 1), deep K
+CB64L_G1 = ("cb", 64, 1, 1, 0, 1)                                      # lean 64-tile gather
+
+
+def test_big_gather_cases_reach_their_cb_instance():
+    _, inst, _ = _launches("big_gather_k40", "relax0")
+    assert inst[CB128_G1] == [6]  # the parent's 300-row CB: 2 x 128 + 44, partial edge tiles
+    _, inst, _ = _launches("big_gather_k100", "relax0")
+    assert CB64L_G1 in inst and not any(k[0] == "cb" and k[1] == 128 for k in inst)  # 64 < K <= 128: lean although wide
+    symb, inst, calls = _launches("big_gather_k200", "relax0")
+    assert CB128_G0 in inst and ("panel", 128, 0, 1, 0, 0) in inst
+    assert calls["asm_tiled"] >= 1 and calls["trsm_pre"] >= 1 and calls["trsm_partial"] >= 1 and calls["trsm_fused"] >= 1
+    assert sorted(symb.supernodes()["m"].tolist())[-3:] == [642, 677, 713]  # above ASM_TILE_MIN_M and 2 x TRSM_ROWS
+    _, inst, calls = _launches("big_gather_k200", "nbo128")
+    assert ("panel", 128, 0, 0, 0, 0) in inst and ("panel", 64, 1, 0, 0, 0) in inst  # the lookahead stream's instances
+    assert calls["record"] >= 1 and calls["wait"] >= 1
+    _, inst, _ = _launches("big_gather_k200", "nbo192")
+    assert ("panel", 64, 0, 0, 0, 0) in inst  # K = 192: past the lean instance, on the lookahead stream
+    symb, inst, _ = _launches("big_nested_gather", "relax0")
+    assert int(symb.supernodes()["level"].max()) == 3  # four levels: a gather reads a CB a gather wrote
+    assert CB128_G1 in inst and CB64L_G1 in inst
+    symb, inst, _ = _launches("big_fanin40_tile128", "relax0")
+    assert inst[CB128_G1] == [6]
+    assert symb.schedule_digest()["gsegs"] > 40 * 3  # many children in every block of the parent's CB
+
+
+@pytest.mark.parametrize("tag", ["relax0", "default"])
+def test_big_cb_edge_cases_pick_the_tile_per_launch(tag):
+    # the parent's mb x mb CB: 255 stays on 64-tiles, 256 is three 128-tiles, 257 six (the
+    # last row and column of them one wide); the parent survives the default amalgamation
+    want = {"big_cb255": None, "big_cb256": [3], "big_cb257": [6]}
+    for name, tiles in want.items():
+        symb, inst, _ = _launches(name, tag)
+        mb = int(name[-3:])
+        assert (40, 40 + mb) in zip(symb.supernodes()["w"].tolist(), symb.supernodes()["m"].tolist())
+        assert inst.get(CB128_G1) == tiles, (name, inst)
+        assert ("cb", 64, 0, 1, 0, 1) in inst  # the children's CBs, and at 255 the parent's
+
+
+def test_big_cases_that_survive_the_default_amalgamation():
+    whole = []
+    for name in zoo.BIG_FRONTS:
+        a, b = (_partition(sc.Symbolic(zoo.case(name).A, **kw)) for kw in (dict(relax=0), {}))
+        if a == b:
+            whole.append(name)
+    # elsewhere the parent, the front before the root, merges into the root
+    assert whole == ["big_cb255", "big_cb256", "big_cb257"]
+    assert tuple(n for n in zoo.SURVIVE_RELAX if n in zoo.BIG_FRONTS) == tuple(whole)
+
+
+@pytest.mark.parametrize("name", zoo.BIG_FRONTS)
+def test_big_tags_change_what_they_are_named_for(name):
+    _, inst, calls = _launches(name, "tile128")
+    assert all(k[1] == 128 and k[2] == 0 and k[4] == 0 for k in inst)  # every SYRK on 128-tiles, no pre-factor
+    assert calls["trsm_pre"] == 0 and calls["trsm_fused"] >= 1           # so every TRSM is fused
+    _, inst0, calls0 = _launches(name, "relax0")
+    _, _, calls = _launches(name, "trsm_split")
+    assert calls["potrf"] > calls0["potrf"] and calls["trsm_pre"] > calls0["trsm_pre"]
+    _, inst, calls = _launches(name, "nbo128")
+    assert calls["record"] >= 1 and any(k[0] == "panel" and k[3] == 0 for k in inst)  # lookahead-stream updates
+    _, inst, calls = _launches(name, "nbo128_rl")
+    assert calls["record"] == 0 and not any(k[4] for k in inst) and calls["trsm_pre"] == 0
+    _, inst, calls = _launches(name, "tiled_nogather")
+    assert calls["asm_tiled"] >= 1 and calls["asm_cols"] == 0 and not any(k[5] for k in inst)
+    _, _, calls = _launches(name, "allfronts")
+    assert calls["front_small"] == 0
+
+
+def test_big_cases_cover_every_syrk_instance():
+    # over the big_ cases and their tags: every (kind, tile, lean, epi) the schedule's rules
+    # allow, CB launches with and without the gather.  The rules (push_syrk_launch) exclude:
+    # lean CB launches with epi = 0 (lean needs K <= 128, epi = 0 needs K >= 192) and
+    # pre-factoring panel launches with epi = 0 (pf forces epi = 1, plain 64-tiles).
+    # tail = 1 (the re-cut last round of a deep-K CB launch) needs more than 512 tiles of
+    # 128: no small case reaches it, lap48 (tests/test_gpu_parity.py) remains its only cover.
+    seen = set()
+    for name in zoo.BIG_FRONTS:
+        for tag in zoo.tags(name):
+            seen |= set(_launches(name, tag)[1])
+    want = set()
+    for g in (0, 1):
+        want |= {("cb", 64, 0, 0, 0, g), ("cb", 64, 0, 1, 0, g), ("cb", 64, 1, 1, 0, g), ("cb", 128, 0, 0, 0, g),
+                 ("cb", 128, 0, 1, 0, g)}
+    for epi in (0, 1):
+        want |= {("panel", 64, 0, epi, 0, 0), ("panel", 64, 1, epi, 0, 0), ("panel", 128, 0, epi, 0, 0)}
+    want.add(("panel", 64, 0, 1, 1, 0))
+    assert want <= seen, sorted(want - seen)
+    assert ("cb", 64, 1, 0, 0, 0) not in seen and ("cb", 64, 1, 0, 0, 1) not in seen
+    assert not any(k[4] and not k[3] for k in seen)
+
+
+def test_syrk_launches_agree_with_the_digest():
+    for name, tag in (("big_gather_k200", "nbo128"), ("forest", "default"), ("tiny_17", "relax0")):
+        symb = sc.Symbolic(zoo.case(name).A, **zoo.OPTS[tag])
+        d, ls = symb.schedule_digest(), symb.syrk_launches()
+        assert sum(l["kind"] == "panel" for l in ls) == d["calls"]["syrk_panel"]
+        assert sum(l["kind"] == "cb" for l in ls) == d["calls"]["syrk_cb"]
+        assert sum(l["pf"] for l in ls) == d["pf"] and sum(l["tail"] for l in ls) == d["tail_split"]
+        assert all(l["tiles"] >= 1 and l["bt"] in (64, 128) for l in ls)
+        assert symb.schedule_digest() == d  # listing the launches leaves the digest alone
+    symb = sc.Symbolic(zoo.case("big_gather_k200").A, relax=0)
+    assert len(symb.syrk_launches(2, 0, 1)) >= 1 and len(symb.syrk_launches(2, 1, 0)) >= 0
+
+
+# ---- 2c. the debug hooks refuse inconsistent arguments before any device call ----
+def test_kernel_hooks_refuse_bad_arguments():
+    import ctypes
+
+    L = sc.lib()
+    ERR = -1  # SC_ERR_ARG
+    p = ctypes.c_void_p(4096)  # never dereferenced: every call below is refused on its arguments
+    ok = dict(ldc=70, lda=70, M=65, N=64, K=7, bt=64, lean=0, tag=0, epi=0)
+
+    def syrk(**kw):
+        a = dict(ok, **kw)
+        return L.sc_debug_syrk_ex(a.get("C", p), a["ldc"], a.get("A", p), a["lda"], a["M"], a["N"], a["K"], a["bt"],
+                                  a["lean"], a["tag"], a["epi"])
+
+    for bad in (dict(C=None), dict(A=None), dict(M=0), dict(N=0), dict(K=0), dict(N=66), dict(lda=64), dict(ldc=64),
+                dict(bt=32), dict(bt=0), dict(bt=256), dict(bt=128, lean=1), dict(lean=2), dict(lean=-1), dict(tag=2),
+                dict(tag=-1), dict(epi=2), dict(epi=-1), dict(lda=1 << 22), dict(ldc=1 << 22)):
+        assert syrk(**bad) == ERR, bad
+    assert L.sc_debug_syrk(p, 64, p, 70, 65, 64, 7) == ERR  # the old hook goes through the new one
+
+    info = ctypes.c_int32(-7)
+
+    def panel(m=200, w=130, k0=0, mode=1, F=p, inf=ctypes.byref(info)):
+        return L.sc_debug_panel(F, m, w, k0, mode, inf)
+
+    for bad in (dict(F=None), dict(inf=None), dict(m=0), dict(w=0), dict(w=201), dict(k0=-64), dict(k0=32), dict(k0=192),
+                dict(mode=-1), dict(mode=4), dict(k0=128, mode=1), dict(k0=128, mode=2), dict(k0=64, mode=3),
+                dict(k0=0, mode=3), dict(m=(1 << 22) + 1, w=64)):
+        assert panel(**bad) == ERR, bad
+    assert info.value == -7  # untouched
+
+    symb = sc.Symbolic(zoo.case("tiny_17").A)
+    out = np.zeros(8, dtype=np.int64)
+    ptr = out.ctypes.data_as(ctypes.c_void_p)
+    for args in ((None, 1, 0, 0, ptr, 8), (symb.h, 0, 0, 0, ptr, 8), (symb.h, 2, 2, 0, ptr, 8), (symb.h, 1, -1, 0, ptr, 8),
+                 (symb.h, 1, 0, 3, ptr, 8), (symb.h, 1, 0, 0, ptr, -1), (symb.h, 1, 0, 0, None, 8)):
+        assert L.sc_debug_schedule_syrk(*args) == ERR, args
+
+
 # ---- 3. multi-rank plans on the host ----
 @pytest.mark.parametrize("nranks", [2, 4])
-@pytest.mark.parametrize("name", ["forest", "fanin300_mid_cb"])
+@pytest.mark.parametrize("name", ["forest", "fanin300_mid_cb", "big_gather_k200"])
 def test_multi_rank_plans_build(name, nranks):
     for kw in (dict(relax=0), {}):
         symb = sc.Symbolic(zoo.case(name).A, **kw)

@@ -1,5 +1,6 @@
 """SPD matrices whose assembly tree is prescribed front by front, a catalogue of them that
-aims at structural code paths (long chains, fan-in, forests, the tiny-tree limits), and
+aims at structural code paths (long chains, fan-in, forests, the tiny-tree limits, large
+fronts whose updates run on every instance of the MFMA SYRK: the big_ cases), and
 long-double references.  Helper module (not collected by pytest), used by
 tests/test_zoo_cpu.py and tests/test_zoo_gpu.py.
 
@@ -312,6 +313,44 @@ def _forest():
     return side_by_side(one, [(2, -1, 0, "head")], small, one, chain, large, [(130, -1, 0, "head")], one)
 
 
+# ---- large fronts: the 128-tile, lean and deep-K SYRK instances on irregular maps ----
+# five children of every kind of row map, CBs from 10 to 300 rows
+KIDS = ((130, 300, "stride"), (70, 257, "rand"), (200, 129, "tail"), (64, 64, "head"), (3, 10, "rand"))
+
+
+def _under(kids, parent, root_w):
+    """kids [(w, mb, pick)] under one parent (w, mb, pick) under a root."""
+    nk = len(kids)
+    return [(w, nk, mb, pick) for (w, mb, pick) in kids] + [parent[:1] + (nk + 1,) + parent[1:],
+                                                            (root_w, -1, 0, "head")]
+
+
+def _big_gather_k200():
+    # fronts of 642, 677 and 713 rows: the write-once assembly's 256-row tiles, the TRSM's
+    # 256-row workgroups, the selected inversion's K split
+    kids = ((130, 512, "stride"), (70, 257, "rand"), (257, 420, "rand"), (64, 64, "head"))
+    return _under(kids, (200, 513, "stride"), 530)
+
+
+def _big_nested_gather():
+    # four levels: the parent gathers the mid front's CB, which a gather wrote
+    return [(90, 3, 200, "rand"), (20, 3, 260, "stride"), (5, 3, 70, "tail"), (140, 5, 280, "rand"),
+            (66, 5, 257, "stride"), (70, 6, 300, "rand"), (310, -1, 0, "head")]
+
+
+def _big_fanin40_tile128():
+    kids = [(1 + i % 7, 60 + (37 * i) % 200, PICKS[i % 4]) for i in range(40)]
+    return _under(kids, (150, 300, "rand"), 310)
+
+
+def _big_cb(mb):
+    # the parent's CB is mb x mb: 255 stays on 64-tiles, 256 is three 128-tiles, 257 six.  The
+    # root's second child comes after the parent, so the parent is not the front before its
+    # parent and the default amalgamation cannot merge it
+    return [(129, 3, 200, "rand"), (8, 3, 30, "stride"), (64, 3, mb, "tail"), (40, 5, mb, "tail"),
+            (25, 5, 30, "rand"), (mb + 3, -1, 0, "head")]
+
+
 SPECS = {
     "tiny_hbm_pairs": _tiny_hbm_pairs,
     "tiny_16_m64": lambda: _tiny_limits(15, 64),
@@ -327,17 +366,56 @@ SPECS = {
     "edges_a": lambda: _edges([(63, 1), (64, 64), (65, 63), (1, 128), (1, 129)], 200),
     "edges_b": lambda: _edges([(128, 255), (129, 257), (64, 256), (127, 129)], 330),
     "forest": _forest,
+    "big_gather_k40": lambda: _under(KIDS, (40, 300, "stride"), 320),
+    "big_gather_k100": lambda: _under(KIDS[:4], (100, 300, "stride"), 320),
+    "big_gather_k200": _big_gather_k200,
+    "big_nested_gather": _big_nested_gather,
+    "big_fanin40_tile128": _big_fanin40_tile128,
+    "big_cb255": lambda: _big_cb(255),
+    "big_cb256": lambda: _big_cb(256),
+    "big_cb257": lambda: _big_cb(257),
 }
 NAMES = tuple(SPECS)
+BIG_FRONTS = tuple(n for n in NAMES if n.startswith("big_"))
 MODES = ("dd", "llt")
 TINY = ("tiny_hbm_pairs", "tiny_16_m64", "tiny_17", "tiny_m65", "tiny_lds_under", "tiny_lds_over")
 # cases whose structure is meant to survive the default relaxation (the chains need relax=0)
-SURVIVE_RELAX = ("tiny_hbm_pairs", "star300_large_root", "star100_small_root", "fanin300_mid_cb")
+SURVIVE_RELAX = ("tiny_hbm_pairs", "star300_large_root", "star100_small_root", "fanin300_mid_cb", "big_cb255",
+                 "big_cb256", "big_cb257")
 # cases with large fronts (m > 128 somewhere)
 LARGE = ("chain300_edges", "chain_into_large_tail", "star300_large_root", "fanin300_mid_cb", "edges_a", "edges_b",
-         "forest")
-# too many entries for a dense inverse to be the quick reference
+         "forest") + BIG_FRONTS
+# too many entries for a dense inverse to be the quick reference (the big_ cases have n <= 1251:
+# the dense inverse stays their reference)
 BIG = ("star300_large_root", "star100_small_root", "fanin300_mid_cb")
+
+
+# analysis options by tag (the GPU tests factor under them, the host tests read their schedules)
+OPTS = {
+    "relax0": dict(relax=0),
+    "default": {},
+    "allfronts": dict(relax=0, small_front_max=0),       # every front through the blocked MFMA path
+    "tiled_nogather": dict(relax=0, asm_tile_min_m=1, cb_gather=0),  # tiled assembly, CBs assembled, not gathered
+    # 128-column slabs: slab ends, the lookahead stream and its panel instances (epi = 0)
+    "nbo128": dict(relax=0, panel_nb_outer=128),
+    "nbo128_rl": dict(relax=0, panel_nb_outer=128, inner_order=0, lookahead=0),  # right-looking, one stream
+    # 192-column slabs: outer updates deeper than the lean instance takes (K = 192), on the lookahead stream
+    "nbo192": dict(relax=0, panel_nb_outer=192),
+    "tile128": dict(relax=0, syrk_tile=128),             # every SYRK on 128-tiles, every TRSM fused
+    "trsm_split": dict(relax=0, trsm_split_wg=1),        # every full block: POTRF launch + prefactored TRSM
+}
+BIG_TAGS = ("relax0", "default", "allfronts", "tiled_nogather", "nbo128", "nbo128_rl", "tile128", "trsm_split")
+
+
+def tags(name):
+    if name in BIG_FRONTS:
+        return list(BIG_TAGS) + (["nbo192"] if name == "big_gather_k200" else [])
+    t = ["relax0", "default"]
+    if name in LARGE:
+        t.append("allfronts")
+    if name.startswith("edges_"):
+        t.append("tiled_nogather")
+    return t
 
 
 @functools.lru_cache(maxsize=None)
