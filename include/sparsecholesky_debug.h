@@ -38,6 +38,17 @@ int64_t sc_debug_syrk_ex(double* dC, int32_t ldc, const double* dA, int32_t lda,
  * anything else returns SC_ERR_ARG before any device call.  *info receives the status
  * word: 0, or the first failing column of the panel + 1. */
 int64_t sc_debug_panel(double* dF, int32_t m, int32_t w, int32_t k0, int32_t mode, int32_t* info);
+/* The two kernels of one block step of sc_updown_host on block k0 (a multiple of 64, nb =
+ * min(64, w - k0) columns) of a caller's m x w front panel (device, column-major, ld = m, 1
+ * <= w <= m) and a caller's m x 16 workspace dW (device, ROW-major: entry (front row i,
+ * column c) at 16 i + c), through a one-front plan whose row list is the identity: the
+ * block kernel on rows [k0, k0 + nb) ([L11 W1] T = [L11' 0], those rows of dW zeroed),
+ * then the row kernel on rows [k0 + nb, m) ([L21 W2] T in place).  sign +1 / -1.  Rows of
+ * dF and dW above k0, other columns and the strict upper triangle of the diagonal block
+ * are neither read nor written.  *info: 0, or the failing column of the panel + 1 of a
+ * downdate (nothing of the block is then written). */
+int64_t sc_debug_updown_block(double* dF, int32_t m, int32_t w, int32_t k0, double* dW, int32_t sign,
+                              int32_t* info);
 /* Best wall time (ms) of reps synchronous factorizations from device values
  * (sc_factor_device(num, d_Ax, 1): launch, run, status read-back), timed in C. */
 int64_t sc_debug_time_factor(sc_numeric* num, const double* d_Ax, int32_t reps, double* best_ms);

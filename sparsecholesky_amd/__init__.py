@@ -143,6 +143,8 @@ _SIGS = [
     ("sc_selinv_diag_device", _I64, [_P, _P]),
     ("sc_selinv_export", _I64, [_P, _P, _P, _P]),
     ("sc_selinv_flops", _I64, [_P, C.POINTER(_D)]),
+    ("sc_updown_check", _I64, [_P, _I32, _P, _P, _P, _P]),
+    ("sc_updown_host", _I64, [_P, _I32, _I32, _P, _P, _P]),
     ("sc_etree", _I64, [_I64, _P, _P, _P]),
     ("sc_post_order", _I64, [_I64, _P, _P]),
     ("sc_col_count", _I64, [_I64, _P, _P, _P, _P, _P]),
@@ -168,6 +170,7 @@ _SIGS = [
     ("sc_debug_syrk", _I64, [_P, _I32, _P, _I32, _I32, _I32, _I32]),
     ("sc_debug_syrk_ex", _I64, [_P, _I32, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32]),
     ("sc_debug_panel", _I64, [_P, _I32, _I32, _I32, _I32, C.POINTER(_I32)]),
+    ("sc_debug_updown_block", _I64, [_P, _I32, _I32, _I32, _P, _I32, C.POINTER(_I32)]),
     ("sc_debug_bench", _I64, [_I32, _I32, _I32, _I32, _I32, C.POINTER(_D)]),
     ("sc_device_count", _I64, []),
     ("sc_debug_chain_stamps", _I64, [_P, _I32, _P, _I64]),
@@ -487,6 +490,28 @@ def default_options(**kw) -> Options:
     return o
 
 
+def _updown_W(W, n: int):
+    """(Wp, Wi, Wx, k) of an update matrix: a (Wp, Wi, Wx) triple as it is, a dense (n, k)
+    array by its nonzeros."""
+    if isinstance(W, tuple):
+        Wp, Wi, Wx = W
+        Wp = np.ascontiguousarray(Wp, dtype=np.int64)
+        Wi = np.ascontiguousarray(Wi, dtype=np.int32)
+        Wx = np.ascontiguousarray(Wx, dtype=np.float64)
+        if len(Wp) < 1 or len(Wi) != len(Wx) or len(Wi) < int(Wp[-1]):
+            raise ValueError("updown: (Wp, Wi, Wx) is not a CSC triple")
+        return Wp, Wi, Wx, len(Wp) - 1
+    D = np.asarray(W, dtype=np.float64)
+    if D.ndim == 1:
+        D = D[:, None]
+    if D.ndim != 2 or D.shape[0] != n:
+        raise ValueError(f"updown: W has shape {D.shape}, the matrix {n} rows")
+    cols, rows = np.nonzero(D.T)
+    Wp = np.zeros(D.shape[1] + 1, dtype=np.int64)
+    np.cumsum(np.bincount(cols, minlength=D.shape[1]), out=Wp[1:])
+    return Wp, rows.astype(np.int32), np.ascontiguousarray(D.T[cols, rows]), D.shape[1]
+
+
 class Symbolic:
     """Host symbolic analysis (schol + supernodal plan)."""
 
@@ -544,6 +569,19 @@ class Symbolic:
         lev = np.zeros(max(ns, 1), dtype=np.int32)
         _check(lib().sc_symbolic_supernodes(self.h, _ptr(st), _ptr(m), _ptr(par), _ptr(lev)), "supernodes")
         return dict(start=st, m=m[:ns], w=np.diff(st), parent=par[:ns], level=lev[:ns])
+
+    def updown_check(self, W) -> tuple:
+        """Admissibility of W for :meth:`Numeric.update` / :meth:`Numeric.downdate`, on the host
+        alone: ``(first_col, path)`` with ``first_col[c]`` the first row of column c in the order
+        of P A P^T (-1: empty column) and ``path`` a dict of what one sweep touches:
+        ``supernodes``, ``blocks`` (64-column block steps) and ``panel_entries`` (sum of m w).
+        W as for :meth:`Numeric.updown`.  Raises :class:`LibraryError` naming the column and
+        the row when a column is not admissible."""
+        Wp, Wi, _, k = _updown_W(W, self.n)
+        first = np.zeros(max(k, 1), dtype=np.int32)
+        path = np.zeros(3, dtype=np.int64)
+        _check(lib().sc_updown_check(self.h, k, _ptr(Wp), _ptr(Wi), _ptr(first), _ptr(path)), "updown_check")
+        return first[:k], dict(supernodes=int(path[0]), blocks=int(path[1]), panel_entries=int(path[2]))
 
     def owner_map(self, nranks: int):
         ns = self.stats()["n_supernodes"]
@@ -851,6 +889,24 @@ class Numeric:
         if st > 0:
             raise LibraryError(f"logdet: A is not positive definite (column {st})")
         return v.value
+
+    def updown(self, W, sign: int) -> int:
+        """L <- factor of P (A + sign W W^T) P^T in place on the GPU (sc_updown_host), sign +1
+        or -1.  W: a dense (n, k) array whose nonzeros are the pattern, or a CSC triple
+        ``(Wp, Wi, Wx)`` (explicit zeros count), rows in A's own numbering; every column must
+        be admissible (:meth:`Symbolic.updown_check`).  Returns the status: 0, or the failing
+        column + 1 of a downdate that leaves the matrix not positive definite (the handle's
+        status until the next :meth:`factor`)."""
+        Wp, Wi, Wx, k = _updown_W(W, self.symb.n)
+        return _check(lib().sc_updown_host(self.h, int(sign), k, _ptr(Wp), _ptr(Wi), _ptr(Wx)), "updown")
+
+    def update(self, W) -> int:
+        """A <- A + W W^T (:meth:`updown` with sign +1)."""
+        return self.updown(W, 1)
+
+    def downdate(self, W) -> int:
+        """A <- A - W W^T (:meth:`updown` with sign -1)."""
+        return self.updown(W, -1)
 
     def selinv(self) -> int:
         """Selected inversion: every entry of A^-1 on the pattern of L into the handle's Z

@@ -578,6 +578,62 @@ int64_t sc_debug_selinv_cols(sc_numeric* num, int64_t j0, int64_t j1, int64_t* c
     return rc;
 }
 
+// ---- rank-k update / downdate ----
+static int64_t updown_args(const void* handle, int32_t k, const int64_t* Wp, const int32_t* Wi, const char* who) {
+    const char* bad = nullptr;
+    if (!handle)
+        bad = "null handle";
+    else if (k < 0)
+        bad = "k < 0";
+    else if (k > 0 && !Wp)
+        bad = "null Wp";
+    else if (k > 0 && !Wi && Wp[k] > 0)
+        bad = "null Wi";
+    if (!bad) return SC_OK;
+    g_last_error = std::string(who) + ": " + bad;
+    return SC_ERR_ARG;
+}
+
+int64_t sc_updown_check(const sc_symbolic* sym, int32_t k, const int64_t* Wp, const int32_t* Wi, int32_t* first_col,
+                        int64_t* path) {
+    int64_t rc = updown_args(sym, k, Wp, Wi, "sc_updown_check");
+    if (rc != SC_OK) return rc;
+    if (path) path[0] = path[1] = path[2] = 0;
+    if (k == 0 || sym->S.n == 0) {
+        for (int32_t c = 0; first_col && c < k; ++c) first_col[c] = -1;
+        return SC_OK;
+    }
+    try {
+        std::string err;
+        rc = sc::updown_check(sym->S, k, Wp, Wi, first_col, path, "sc_updown_check", err);
+        if (rc < 0) g_last_error = err;
+        return rc;
+    } catch (const std::bad_alloc&) {
+        return SC_ERR_NOMEM;
+    }
+}
+
+int64_t sc_updown_host(sc_numeric* num, int32_t sign, int32_t k, const int64_t* Wp, const int32_t* Wi,
+                       const double* Wx) {
+    int64_t rc = updown_args((num && num->N) ? num : nullptr, k, Wp, Wi, "sc_updown_host");
+    if (rc != SC_OK) return rc;
+    if (sign != 1 && sign != -1) {
+        g_last_error = "sc_updown_host: sign must be +1 (update) or -1 (downdate)";
+        return SC_ERR_ARG;
+    }
+    if (k > 0 && !Wx && Wp[k] > 0) {
+        g_last_error = "sc_updown_host: null Wx";
+        return SC_ERR_ARG;
+    }
+    try {
+        rc = sc::numeric_updown_host(*num->N, sign, k, Wp, Wi, Wx);
+        if (rc < 0) g_last_error = num->N->err;
+        return rc;
+    } catch (const std::bad_alloc&) {
+        return SC_ERR_NOMEM;
+    }
+}
+
 // ---- reference-API helpers ----
 int64_t sc_etree(int64_t n, const int64_t* Ap, const int32_t* Ai, int32_t* parent) {
     if (n < 0 || !Ap || !parent) return SC_ERR_ARG;
@@ -820,6 +876,12 @@ int64_t sc_debug_syrk_ex(double* dC, int32_t ldc, const double* dA, int32_t lda,
 int64_t sc_debug_panel(double* dF, int32_t m, int32_t w, int32_t k0, int32_t mode, int32_t* info) {
     if (!dF || !info) return SC_ERR_ARG;
     return sc::debug_panel(dF, m, w, k0, mode, info);
+}
+
+int64_t sc_debug_updown_block(double* dF, int32_t m, int32_t w, int32_t k0, double* dW, int32_t sign,
+                              int32_t* info) {
+    if (!dF || !dW || !info) return SC_ERR_ARG;
+    return sc::debug_updown_block(dF, m, w, k0, dW, sign, info);
 }
 
 int64_t sc_debug_bench(int32_t which, int32_t M, int32_t K, int32_t reps, int32_t arg, double* tflops) {

@@ -1,6 +1,6 @@
 // Debug and microbenchmark hooks (sc_debug_syrk, sc_debug_syrk_ex, sc_debug_panel,
-// sc_debug_bench): the SYRK and panel kernels on caller data, kernel ceilings on synthetic
-// operands.
+// sc_debug_updown_block, sc_debug_bench): the SYRK, panel and update / downdate kernels on
+// caller data, kernel ceilings on synthetic operands.
 #include "numeric_impl.hpp"
 
 namespace sc {
@@ -134,6 +134,52 @@ int64_t debug_panel(double* dF, int m, int w, int k0, int mode, int32_t* info) {
         else
             *info = (st == ARMED || st <= 0) ? 0 : st;
     }
+    return rc;
+}
+
+int64_t debug_updown_block(double* dF, int m, int w, int k0, double* dW, int sign, int32_t* info) {
+    if (!dF || !dW || !info || m < 1 || m > (1 << 22) || w < 1 || w > m || k0 < 0 || k0 >= w || k0 % PNB != 0 ||
+        (sign != 1 && sign != -1))
+        return SC_ERR_ARG;
+    // one front whose row list is the identity: dW is the workspace itself; post: none (the
+    // status word numbers the panel's columns)
+    const int32_t hs[2] = {0, w}, hm[1] = {m};
+    const int64_t ho[1] = {0}, hrp[2] = {0, m};
+    std::vector<int32_t> rows((size_t)m);
+    for (int i = 0; i < m; ++i) rows[(size_t)i] = i;
+    void *d_s = nullptr, *d_m = nullptr, *d_o = nullptr, *d_rp = nullptr, *d_r = nullptr, *d_t = nullptr, *d_i = nullptr;
+    int64_t rc = SC_OK;
+    if (hipMalloc(&d_s, 8) || hipMalloc(&d_m, 4) || hipMalloc(&d_o, 8) || hipMalloc(&d_rp, 16) ||
+        hipMalloc(&d_r, (size_t)m * 4) || hipMalloc(&d_t, (size_t)UPD_K * UPD_K * sizeof(double)) || hipMalloc(&d_i, 4))
+        rc = SC_ERR_DEVMEM;
+    else if (hipMemcpy(d_s, hs, 8, hipMemcpyHostToDevice) || hipMemcpy(d_m, hm, 4, hipMemcpyHostToDevice) ||
+             hipMemcpy(d_o, ho, 8, hipMemcpyHostToDevice) || hipMemcpy(d_rp, hrp, 16, hipMemcpyHostToDevice) ||
+             hipMemcpy(d_r, rows.data(), (size_t)m * 4, hipMemcpyHostToDevice) || hipMemset(d_i, 0x7f, 4))
+        rc = SC_ERR_HIP;
+    if (rc == SC_OK) {
+        UpdPlan P {};
+        P.sn_start = (const int32_t*)d_s;
+        P.sn_m = (const int32_t*)d_m;
+        P.panel_off = (const int64_t*)d_o;
+        P.rows_ptr = (const int64_t*)d_rp;
+        P.rows = (const int32_t*)d_r;
+        P.panel_pool = dF;
+        P.wd = dW;
+        P.tbuf = (double*)d_t;
+        P.info = (int32_t*)d_i;
+        P.post = nullptr;
+        hipError_t e = launch_updown_block(P, 0, k0, sign, nullptr);
+        if (e == hipSuccess) e = launch_updown_rows(P, 0, k0, m - std::min(w, k0 + PNB), nullptr);
+        const hipError_t e2 = hipDeviceSynchronize();
+        int32_t st = 0;
+        const hipError_t e3 = e2 == hipSuccess ? hipMemcpy(&st, d_i, 4, hipMemcpyDeviceToHost) : e2;
+        if (e != hipSuccess || e2 != hipSuccess || e3 != hipSuccess)
+            rc = SC_ERR_HIP;
+        else
+            *info = (st == UPD_ARMED || st <= 0) ? 0 : st;
+    }
+    for (void* p : {d_s, d_m, d_o, d_rp, d_r, d_t, d_i})
+        if (p) (void)hipFree(p);
     return rc;
 }
 

@@ -3347,6 +3347,232 @@ __global__ __launch_bounds__(LOGDET_NT) void sel_diag_kernel(SelPlan P, int ns, 
     diag[post[j]] = P.zpanel[P.panel_off[lo] + (int64_t)(j - P.sn_start[lo]) * (P.sn_m[lo] + 1)];
 }
 
+// ---------------------------------------------------------------------------
+// Rank-k update / downdate of the factor (updown.cpp).
+//
+// Block (s, k0) of a touched front, nb columns: the nb x nb triangle L11 and the nb x 16
+// rows W1 of the workspace satisfy [L11 W1] T = [L11' 0] for a product T of plane
+// rotations (sign > 0) or hyperbolic rotations (sign < 0), pivot by pivot, column of W by
+// column of W.  A rotation acts on two columns, so every row is transformed independently
+// once the pivot row has fixed the coefficients: one thread per row, the row's 16 W entries
+// in registers, its L11 entry of the current pivot column in LDS.  T is accumulated the same
+// way from the rows of the identity (threads nb .. 2 nb + 16).  Then the rows below take
+// [L21 W2] T as an fp64 MFMA product.  No atomics but the status report; fixed order.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void updown_scatter_kernel(double* __restrict__ wd, const int64_t* __restrict__ idx,
+                                                            const double* __restrict__ val, int64_t count) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e < count) wd[idx[e]] = val[e];
+}
+
+__global__ __launch_bounds__(256) void updown_block_kernel(UpdPlan P, int s, int k0, int sign) {
+    constexpr int LDL = PNB + 1, LDT = UPD_K + 1;  // odd strides: a column's rows fall into distinct banks
+    __shared__ double Ls[PNB * LDL];            // L11(i, j), i >= j, at j LDL + i
+    __shared__ double Ts[UPD_K * LDT];          // T(k, j) at k LDT + j, written out at the end
+    __shared__ double cs[2][UPD_W], sn[2][UPD_W], ri[2][UPD_W];  // the rotations of a pivot, double-buffered
+    __shared__ int fail[2];                     // per buffer: its pivot is not positive
+    if (__atomic_load_n(P.info, __ATOMIC_RELAXED) != UPD_ARMED) return;  // an earlier block of the sweep failed
+    const int tid = threadIdx.x;
+    const int m = P.sn_m[s], c0 = P.sn_start[s], w = P.sn_start[s + 1] - c0;
+    const int nb = min(PNB, w - k0);
+    double* __restrict__ L = P.panel_pool + P.panel_off[s] + (int64_t)k0 * m + k0;  // L11(i, j) at j m + i
+    const bool isrow = tid < nb;                         // row tid of [L11 W1]
+    const bool istrow = tid >= nb && tid < 2 * nb + UPD_W;  // row tid - nb of the identity: a row of T
+    const int trow = tid - nb;
+    const int tk = trow < nb ? trow : PNB + (trow - nb);  // its index in T's numbering
+    for (int e = tid; e < UPD_K * LDT; e += 256) Ts[e] = 0.0;
+    for (int e = tid; e < nb * nb; e += 256) {
+        const int i = e % nb, j = e / nb;
+        if (i >= j) Ls[j * LDL + i] = L[(int64_t)j * m + i];
+    }
+    double wr[UPD_W];
+    double* __restrict__ wrow = P.wd + (int64_t)UPD_W * (c0 + k0 + tid);  // pivots are the front's first rows
+#pragma unroll
+    for (int c = 0; c < UPD_W; ++c) wr[c] = isrow ? wrow[c] : ((istrow && trow - nb == c) ? 1.0 : 0.0);
+    if (tid < 2) fail[tid] = 0;
+    __syncthreads();
+    // The rotations of pivot j from row j as it stands (after it has taken the rotations of
+    // pivot j - 1), by every lane of wave 0 (the block's rows are its lanes): the 16 entries
+    // b_c of the row are broadcast from lane j; with R_c = L(j, j)^2 + sign (b_0^2 + .. +
+    // b_c^2) and r_c = sqrt(R_c), rotation c takes the diagonal from r_{c-1} to r_c, and lane
+    // c forms R_{c-1} and R_c by the same sequence of additions as its neighbours (so the
+    // r it shares with them has the same bits), then its own square roots and quotients.  A
+    // zero b_c adds an exact zero and its rotation is exactly the identity.
+    auto rotations = [&](int j, int buf) {
+        double b[UPD_W];
+#pragma unroll
+        for (int c = 0; c < UPD_W; ++c) b[c] = readlane_f64(wr[c], j);
+        if (tid == j) {
+#pragma unroll
+            for (int c = 0; c < UPD_W; ++c) wr[c] = 0.0;
+        }
+        const double a0 = Ls[j * LDL + j];
+        const int c = tid & (UPD_W - 1);
+        double R = a0 * a0, Sp = R, S = R, bc = 0.0;
+        bool before = false, upto = false;  // an active column before c / up to c
+#pragma unroll
+        for (int i = 0; i < UPD_W; ++i) {
+            const double q = b[i] * b[i];
+            R = sign > 0 ? R + q : R - q;
+            if (i < c) {
+                Sp = R;
+                before = before || b[i] != 0.0;
+            }
+            if (i <= c) {
+                S = R;
+                upto = upto || b[i] != 0.0;
+            }
+            if (i == c) bc = b[i];
+        }
+        const double rp = before ? sqrt(Sp) : a0, r = upto ? sqrt(S) : a0;
+        double cc = 1.0, ss = 0.0, rr = 1.0;
+        bool bad = false;
+        if (bc != 0.0) {
+            bad = sign < 0 && (!(S > 0.0) || !(S < INFINITY));  // the new squared diagonal
+            if (sign > 0) {
+                cc = rp / r;
+                ss = bc / r;
+            } else {
+                cc = r / rp;
+                ss = bc / rp;
+                rr = rp / r;
+            }
+        }
+        if (tid < UPD_W) {
+            cs[buf][c] = cc;
+            sn[buf][c] = ss;
+            ri[buf][c] = rr;
+            if (c == UPD_W - 1) Ls[j * LDL + j] = r;
+            if (bad) {
+                report_fail(P.info, P.post, c0 + k0 + j);
+                fail[buf] = 1;
+            }
+        }
+    };
+    if (tid < 64) rotations(0, 0);
+    __syncthreads();
+    for (int j = 0; j < nb; ++j) {
+        const int buf = j & 1;
+        // uniform: written before the last barrier, not again until after the next one.  L is
+        // left partly modified, the sweep's later launches return at once
+        if (fail[buf]) return;
+        if ((isrow && tid > j) || istrow) {
+            double cj[UPD_W], sj[UPD_W], rj[UPD_W];
+#pragma unroll
+            for (int c = 0; c < UPD_W; ++c) {
+                cj[c] = cs[buf][c];
+                sj[c] = sn[buf][c];
+                rj[c] = ri[buf][c];
+            }
+            double l = isrow ? Ls[j * LDL + tid] : (trow == j ? 1.0 : 0.0);
+#pragma unroll
+            for (int c = 0; c < UPD_W; ++c) {
+                if (sj[c] == 0.0) continue;  // the same for every thread
+                if (sign > 0) {
+                    const double t = cj[c] * l + sj[c] * wr[c];
+                    wr[c] = cj[c] * wr[c] - sj[c] * l;
+                    l = t;
+                } else {  // mixed form: the new L first, the new W from it
+                    l = (l - sj[c] * wr[c]) * rj[c];
+                    wr[c] = cj[c] * wr[c] - sj[c] * l;
+                }
+            }
+            if (isrow)
+                Ls[j * LDL + tid] = l;
+            else
+                Ts[tk * LDT + j] = l;
+        }
+        // row j + 1 is final for its own pivot: its rotations go to the other buffer while the
+        // other waves still read this one
+        if (tid < 64 && j + 1 < nb) rotations(j + 1, buf ^ 1);
+        __syncthreads();
+    }
+    if (istrow) {
+#pragma unroll
+        for (int c = 0; c < UPD_W; ++c) Ts[tk * LDT + PNB + c] = wr[c];
+    }
+    if (isrow) {
+#pragma unroll
+        for (int c = 0; c < UPD_W; ++c) wrow[c] = 0.0;
+    }
+    __syncthreads();
+    for (int e = tid; e < UPD_K * UPD_K; e += 256) P.tbuf[e] = Ts[(e / UPD_K) * LDT + e % UPD_K];
+    for (int e = tid; e < nb * nb; e += 256) {
+        const int i = e % nb, j = e / nb;
+        if (i >= j) L[(int64_t)j * m + i] = Ls[j * LDL + i];
+    }
+}
+
+// The hot path: out^T = T^T [L21 W2]^T, so that the 16 lanes of an MFMA column are 16
+// consecutive front rows (contiguous loads and stores of the panel's columns).  A operand:
+// T(k, j) from LDS (M index j, the output column); B operand: the row's entries, K = 80 of
+// them in registers, loaded before anything is stored.
+__global__ __launch_bounds__(256) void updown_rows_kernel(UpdPlan P, int s, int k0) {
+    __shared__ double Ts[UPD_K * UPD_K];
+    if (__atomic_load_n(P.info, __ATOMIC_RELAXED) != UPD_ARMED) return;
+    const int tid = threadIdx.x, lane = tid & 63, wv = wave_id();
+    const int il = lane & 15, kq = lane >> 4;
+    const int m = P.sn_m[s], w = P.sn_start[s + 1] - P.sn_start[s];
+    const int nb = min(PNB, w - k0);
+    for (int e = tid; e < UPD_K * UPD_K; e += 256) Ts[e] = P.tbuf[e];
+    __syncthreads();
+    const int row0 = k0 + nb + UPD_ROWS * (int)blockIdx.x + 16 * wv;
+    if (row0 >= m) return;  // wave-uniform, after the only barrier
+    const int i = row0 + il;
+    const bool valid = i < m;
+    double* __restrict__ Lc = P.panel_pool + P.panel_off[s] + (int64_t)k0 * m;  // column k of the block at k m
+    const int64_t gr = valid ? (int64_t)P.rows[P.rows_ptr[s] + i] : 0;
+    double* __restrict__ wrow = P.wd + UPD_W * gr;
+    constexpr int KS = UPD_K / 4, KL = PNB / 4, MT = UPD_K / 16;
+    double x[KS];
+#pragma unroll
+    for (int ks = 0; ks < KL; ++ks) {
+        const int k = 4 * ks + kq;
+        x[ks] = (valid && k < nb) ? Lc[(int64_t)k * m + i] : 0.0;
+    }
+#pragma unroll
+    for (int ks = KL; ks < KS; ++ks) x[ks] = valid ? wrow[4 * (ks - KL) + kq] : 0.0;
+    double4_t acc[MT];
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) acc[mt] = double4_t {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) {
+        if (ks < KL && 4 * ks >= nb) continue;  // wave-uniform: rows of T past a partial block are zero
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) {
+            if (mt < MT - 1 && 16 * mt >= nb) continue;
+            acc[mt] = __builtin_amdgcn_mfma_f64_16x16x4f64(Ts[(4 * ks + kq) * UPD_K + 16 * mt + il], x[ks], acc[mt], 0, 0, 0);
+        }
+    }
+    if (!valid) return;
+#pragma unroll
+    for (int mt = 0; mt < MT - 1; ++mt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int j = 16 * mt + MFMA_F64_ROW(lane, r);
+            if (j < nb) Lc[(int64_t)j * m + i] = acc[mt][r];
+        }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) wrow[MFMA_F64_ROW(lane, r)] = acc[MT - 1][r];
+}
+
+hipError_t launch_updown_scatter(double* wd, const int64_t* idx, const double* val, int64_t count, hipStream_t st) {
+    if (count <= 0) return hipSuccess;
+    hipLaunchKernelGGL(updown_scatter_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, wd, idx, val, count);
+    return hipGetLastError();
+}
+
+hipError_t launch_updown_block(const UpdPlan& P, int s, int k0, int sign, hipStream_t st) {
+    hipLaunchKernelGGL(updown_block_kernel, dim3(1), dim3(256), 0, st, P, s, k0, sign);
+    return hipGetLastError();
+}
+
+hipError_t launch_updown_rows(const UpdPlan& P, int s, int k0, int nr, hipStream_t st) {
+    if (nr <= 0) return hipSuccess;
+    hipLaunchKernelGGL(updown_rows_kernel, dim3((unsigned)((nr + UPD_ROWS - 1) / UPD_ROWS)), dim3(256), 0, st, P, s, k0);
+    return hipGetLastError();
+}
+
 hipError_t launch_selinv_w(const SelPlan& P, const int2* tiles, int count, hipStream_t st) {
     if (count <= 0) return hipSuccess;
     hipLaunchKernelGGL(sel_w_kernel, dim3(count), dim3(64 * SEL_NW), 0, st, P, tiles);

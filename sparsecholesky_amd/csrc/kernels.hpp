@@ -237,6 +237,39 @@ hipError_t launch_selinv_push(const SelPlan& P, const int4* tasks, int count, hi
 // diag[post[j]] = Z panel diagonal of internal column j (addressing of launch_logdet)
 hipError_t launch_selinv_diag(const SelPlan& P, int ns, int64_t n, const int32_t* post, double* diag, hipStream_t st);
 
+// ---- rank-k update / downdate of the factor: L <- factor of P (A + sign W W^T) P^T ----
+// (updown.cpp).  The UPD_W columns of a chunk of W ride through the
+// touched supernodes in wd (internal row r, column c at UPD_W r + c).  Per 64-column block
+// (s, k0) of a touched front: [L11 W1] T = [L11' 0] by one workgroup, then [L21 W2] T for
+// the front rows below on v_mfma_f64_16x16x4_f64.  T lives in the index space of UPD_K =
+// 64 + UPD_W: k < nb the block's columns, [nb, 64) zero, 64 + c column c of W.
+constexpr int UPD_W = 16;
+constexpr int UPD_K = PNB + UPD_W;
+constexpr int UPD_ROWS = 64;  // front rows per workgroup of the row kernel (16 per wave)
+constexpr int32_t UPD_ARMED = 0x7f7f7f7f;  // status word before any report (as the factorization arms it)
+struct UpdPlan {
+    const int32_t* sn_start;
+    const int32_t* sn_m;
+    const int64_t* panel_off;
+    const int64_t* rows_ptr;
+    const int32_t* rows;    // front rows (internal numbering), first w = the pivots
+    double* panel_pool;
+    double* wd;             // n x UPD_W workspace
+    double* tbuf;           // UPD_K x UPD_K: T(k, j) at UPD_K k + j
+    int32_t* info;          // min failing natural column + 1 (downdates); a sweep's launches return once it is set
+    const int32_t* post;    // internal -> natural column, or null (identity)
+};
+// wd[idx[e]] = val[e]
+hipError_t launch_updown_scatter(double* wd, const int64_t* idx, const double* val, int64_t count, hipStream_t st);
+// Block (s, k0), nb = min(64, w - k0): rotates W1 (wd rows of the block's pivots) into L11
+// column by column (Givens for sign > 0, hyperbolic in mixed form for sign < 0; a zero
+// entry of W1 is skipped, so an inactive column's part of T is exactly the identity), writes
+// L11' (lower triangle only), zeroes those rows of wd and leaves T in tbuf.
+hipError_t launch_updown_block(const UpdPlan& P, int s, int k0, int sign, hipStream_t st);
+// [L21' W2'] = [L21 W2] T for the nr front rows below the block, W2 gathered from / scattered
+// to wd through the front's row list; a wave loads its 16 rows whole before it stores.
+hipError_t launch_updown_rows(const UpdPlan& P, int s, int k0, int nr, hipStream_t st);
+
 // Small fronts (m <= maxm <= 128): one workgroup per front, factored in registers
 // (4 x 4 tiles per thread); seq: one workgroup runs the fronts in order (a whole
 // small tree in postorder, CBs through HBM).

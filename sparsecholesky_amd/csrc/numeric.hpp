@@ -376,6 +376,15 @@ struct Numeric {
     bool sel_profile = false;          // HIP events around every launch of the next calls
     double sel_ms[4] = {0, 0, 0, 0};   // last profiled call: W, Z_RK, Z_KK, push (ms)
 
+    // rank-k update / downdate (updown.cpp; single-device handles): the n x UPD_W workspace,
+    // the T scratch, the sweep's own status word and the staging of one chunk's entries
+    // (UPD_W columns of at most the longest column of L each), allocated at the first call, kept
+    bool upd_ready = false;
+    UpdPlan UPD {};
+    int64_t* d_uidx = nullptr;
+    double* d_uval = nullptr;
+    int64_t upd_cap = 0;               // entries d_uidx / d_uval hold
+
     std::string err;
 };
 
@@ -454,6 +463,23 @@ int64_t numeric_selinv_export(Numeric& N, int64_t* Lp, int32_t* Li, double* Zx);
 int64_t numeric_selinv_export_cols(Numeric& N, int64_t j0, int64_t j1, int64_t* cp, int32_t* ri, double* rx);
 // Dense flops of the sweep from the symbolic structure (the formula of sc_selinv_flops).
 double selinv_flops(const Symbolic& S);
+// Rank-k update / downdate (updown.cpp).  updown_check: host only.  W (n x k, CSC, rows in
+// A's own numbering) is admissible when every column w, permuted to the order of P A P^T,
+// has struct(w) within struct(L(:, j0)), j0 its smallest row (tested entry by entry with the
+// row-subtree walk of ereach, the pattern of L is never formed).  first_col[k] (may be
+// null): j0 per column, -1 for an empty one; path[3] (may be null): touched supernodes,
+// their 64-column blocks, their panel entries.  SC_ERR_ARG with `err` = who + ": " + reason.
+int64_t updown_check(const Symbolic& S, int32_t k, const int64_t* Wp, const int32_t* Wi, int32_t* first_col,
+                     int64_t* path, const char* who, std::string& err);
+// L <- factor of P (A + sign W W^T) P^T in place, in chunks of UPD_W columns, synchronous
+// on the handle's stream.  Returns SC_OK, or the first failing column + 1 of a downdate
+// that leaves the matrix not positive definite (L partly modified; that becomes the
+// handle's status until the next factorization).
+int64_t numeric_updown_host(Numeric& N, int32_t sign, int32_t k, const int64_t* Wp, const int32_t* Wi,
+                            const double* Wx);
+// The two kernels of one block step on block k0 of a caller's m x w panel and m x UPD_W
+// workspace (device; dW row-major, row = front row), through a one-front plan.
+int64_t debug_updown_block(double* dF, int m, int w, int k0, double* dW, int sign, int32_t* info);
 // Destroys the captured solve and apply graphs (they point at one panel pool).
 void numeric_drop_solve_graphs(Numeric& N);
 int64_t debug_syrk(double* dC, int ldc, const double* dA, int lda, int M, int N, int K);
