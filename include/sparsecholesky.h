@@ -34,7 +34,7 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define SC_VERSION 121 /* still 1.2.1, additive: rank-k update / downdate sc_updown_check / sc_updown_host; still 1.2.1, additive: selected inversion sc_selinv / sc_selinv_diag_host / sc_selinv_diag_device / sc_selinv_export / sc_selinv_flops; still 1.2.1, additive: the factor operators sc_apply_host / sc_apply_device / sc_apply_host_multi / sc_apply_device_multi (enum sc_factor_op) and sc_logdet; still 1.2.1, additive: sc_solve_host_multi / sc_solve_device_multi (nrhs right-hand sides); 1.2.1:small merged fronts amalgamated past relax_wmax (different supernode partition of some inputs, same L); 1.2.0: persistent slab chain options removed; panel_prefactor, dist_local_pieces and SC_ORDER_AMD added; out-of-range lookahead / inner_order / ordering rejected */
+#define SC_VERSION 121 /* still 1.2.1, additive: Schur complement sc_analyze_schur / sc_symbolic_schur / sc_schur_factor_* / sc_schur_matrix_* / sc_schur_condense_*_multi / sc_schur_expand_*_multi; still 1.2.1, additive: rank-k update / downdate sc_updown_check / sc_updown_host; still 1.2.1, additive: selected inversion sc_selinv / sc_selinv_diag_host / sc_selinv_diag_device / sc_selinv_export / sc_selinv_flops; still 1.2.1, additive: the factor operators sc_apply_host / sc_apply_device / sc_apply_host_multi / sc_apply_device_multi (enum sc_factor_op) and sc_logdet; still 1.2.1, additive: sc_solve_host_multi / sc_solve_device_multi (nrhs right-hand sides); 1.2.1:small merged fronts amalgamated past relax_wmax (different supernode partition of some inputs, same L); 1.2.0: persistent slab chain options removed; panel_prefactor, dist_local_pieces and SC_ORDER_AMD added; out-of-range lookahead / inner_order / ordering rejected */
 
 enum sc_status {
     SC_OK = 0,
@@ -437,6 +437,70 @@ int64_t sc_updown_check(const sc_symbolic* sym, int32_t k, const int64_t* Wp, co
                         int32_t* first_col, int64_t* path);
 int64_t sc_updown_host(sc_numeric* num, int32_t sign, int32_t k, const int64_t* Wp, const int32_t* Wi,
                        const double* Wx);
+
+/* Schur complement of a chosen index set on the GPU (MUMPS, PARDISO and cuDSS users know it
+ * as the Schur-complement feature): the caller names ns variables S, the interior I (every
+ * other index) is eliminated, and the dense interface problem comes back:
+ *     S_c = A_SS - A_SI inv(A_II) A_IS,
+ * for substructuring, coupling a sparse block to a dense one, or marginalising a precision
+ * matrix onto a few nodes.  sc_analyze_schur is sc_analyze with S ordered last: the interior
+ * first, ordered by opt->ordering applied to the induced graph A_II (natural: ascending
+ * index), then schur_idx in the GIVEN order, perm[n - ns + q] = schur_idx[q]
+ * (sc_symbolic_perm; always a permutation in effect).  Then P A P^T = L L^T with
+ *     L = [ L_II 0 ; L_SI L_SS ]   and   S_c = L_SS L_SS^T,
+ *     g = b_S - A_SI inv(A_II) b_I = L_SS y_S  with  y = L^-1 P b           (condense),
+ *     x_I  from  L^T (P x) = [ y_I ; L_SS^T x_S ]  for any x_S               (expand),
+ * so that x = A^-1 b when x_S = S_c^-1 g.  The factorization, its schedule and every other
+ * entry point (solves, operators, sc_logdet, sc_selinv, sc_updown_host, the exports) work on
+ * such a handle unchanged: to them it is one more permutation.  schur_idx: ns distinct rows
+ * of A; SC_ERR_ARG with a message naming the entry for a value out of range or given twice,
+ * for ns < 0, ns > n, or a null list with ns > 0.  ns == 0 is sc_analyze; ns == n is legal
+ * (S_c = A in the order of the list).  sc_symbolic_schur returns ns (0 for a plain handle)
+ * and, when schur_idx is not NULL, the list.
+ * Numbering: D = L_SS and S_c are ns x ns, column-major (ldd, lds >= ns), row and column q
+ * standing for schur_idx[q]; G and XS are ns x nrhs in the same order; B and X are n x nrhs
+ * in A's own order, as in sc_solve_*_multi.  D is lower triangular with an exactly zero
+ * upper triangle and equals the trailing block of sc_export_L bit for bit; S_c is written
+ * to both triangles from one computed value, exactly symmetric.  Entries outside the ns x ns
+ * window (the padding of a larger leading dimension) are never written.
+ * sc_schur_expand_*_multi returns in the rows of X at schur_idx the caller's XS bit for bit.
+ * X may be B when ldx == ldb; argument rules of sc_apply_device_multi plus ldg, ldxs >= ns;
+ * nrhs == 0: SC_OK.  Calls are synchronous on the handle's stream.
+ * Status rules of sc_selinv: SC_ERR_STATE before a factorization; a failed factorization
+ * returns its status > 0 and writes nothing; multi-rank and emulated handles SC_ERR_NOTIMPL
+ * with a message; SC_ERR_ARG for a null handle or output or a leading dimension below ns.
+ * On a handle without a Schur set (ns == 0) the factor, matrix and condense calls return
+ * SC_OK and touch nothing; expand is then the solve.
+ * Kernels: a gather copies L_SS out of the finished panels (any path of the factorization
+ * leaves them in one layout) into a buffer of the handle, once per generation of the factor
+ * -- a new sc_factor or an sc_updown_host makes it stale and the next call gathers again, so
+ * no call serves a stale S_c.  S_c = D D^T runs as fp64 MFMA products, one workgroup per
+ * 64 x 64 tile of the lower triangle with K only up to the tile's last column (ns^3 / 3
+ * flops), what lies above the diagonal of D never used.  The partial solves are the panel
+ * family's P, L^-1, L^-T and P^T in panels of 16 columns with a dense triangular product by
+ * D in between.  No atomics, fixed order: every result is bitwise repeatable across calls
+ * and handles, and a column of G or X does not depend on the columns it travels with.
+ * Device memory, counted in sc_numeric_memory info[0], allocated at first use and kept:
+ * D (8 ns^2 bytes), 12 bytes per Schur index, the solves' plan and 4 n bytes of postorder
+ * when no solve or operator has run yet; the partial solves add one n x 16 panel (128 n
+ * bytes) and the panel solves' buffers.  A later call allocates nothing.  The _host forms
+ * stage their arrays in device memory for the length of the call (sc_schur_matrix_host:
+ * 8 ns^2 bytes; the partial solves: their B and G / XS), not counted in info[0]. */
+int64_t sc_analyze_schur(int64_t n, const int64_t* Ap, const int32_t* Ai, const sc_options* opt, int32_t ns,
+                         const int32_t* schur_idx, sc_symbolic** out);
+int64_t sc_symbolic_schur(const sc_symbolic* sym, int32_t* schur_idx);
+int64_t sc_schur_factor_device(sc_numeric* num, double* d_D, int64_t ldd);
+int64_t sc_schur_factor_host(sc_numeric* num, double* D, int64_t ldd);
+int64_t sc_schur_matrix_device(sc_numeric* num, double* d_S, int64_t lds);
+int64_t sc_schur_matrix_host(sc_numeric* num, double* S, int64_t lds);
+int64_t sc_schur_condense_device_multi(sc_numeric* num, int32_t nrhs, const double* d_B, int64_t ldb, double* d_G,
+                                       int64_t ldg);
+int64_t sc_schur_condense_host_multi(sc_numeric* num, int32_t nrhs, const double* B, int64_t ldb, double* G,
+                                     int64_t ldg);
+int64_t sc_schur_expand_device_multi(sc_numeric* num, int32_t nrhs, const double* d_B, int64_t ldb,
+                                     const double* d_XS, int64_t ldxs, double* d_X, int64_t ldx);
+int64_t sc_schur_expand_host_multi(sc_numeric* num, int32_t nrhs, const double* B, int64_t ldb, const double* XS,
+                                   int64_t ldxs, double* X, int64_t ldx);
 
 /* ---------------- reference-API helpers (host) ----------------
  * Each mirrors one reference function, with int64 column pointers. */

@@ -64,6 +64,11 @@ int64_t sc_debug_selinv_times(sc_numeric* num, int32_t profile, double* ms);
  * returns the entry count; a failed factorization's status > 0 cannot be told from a
  * count, so check sc_selinv first. */
 int64_t sc_debug_selinv_cols(sc_numeric* num, int64_t j0, int64_t j1, int64_t* cp, int32_t* ri, double* rx);
+/* The Schur complement's product kernel alone on caller data (device memory, no handle):
+ * dS = dD dD^T for the lower triangle of dD (ns x ns, column-major, ldd, lds >= ns), both
+ * triangles of dS written; what dD holds above its diagonal is never used, nothing outside
+ * the ns x ns window of dS is written.  Synchronous. */
+int64_t sc_debug_schur_llt(const double* dD, int32_t ns, int64_t ldd, double* dS, int64_t lds);
 /* Chain launches (runs of single small-front levels): enable = 1 makes the next
  * eager factorizations record 8 shader-clock stamps per chained front (phase
  * boundaries); enable = 0 copies up to cap of them to out.  Returns the count. */

@@ -145,6 +145,16 @@ _SIGS = [
     ("sc_selinv_flops", _I64, [_P, C.POINTER(_D)]),
     ("sc_updown_check", _I64, [_P, _I32, _P, _P, _P, _P]),
     ("sc_updown_host", _I64, [_P, _I32, _I32, _P, _P, _P]),
+    ("sc_analyze_schur", _I64, [_I64, _P, _P, C.POINTER(Options), _I32, _P, C.POINTER(_P)]),
+    ("sc_symbolic_schur", _I64, [_P, _P]),
+    ("sc_schur_factor_device", _I64, [_P, _P, _I64]),
+    ("sc_schur_factor_host", _I64, [_P, _P, _I64]),
+    ("sc_schur_matrix_device", _I64, [_P, _P, _I64]),
+    ("sc_schur_matrix_host", _I64, [_P, _P, _I64]),
+    ("sc_schur_condense_device_multi", _I64, [_P, _I32, _P, _I64, _P, _I64]),
+    ("sc_schur_condense_host_multi", _I64, [_P, _I32, _P, _I64, _P, _I64]),
+    ("sc_schur_expand_device_multi", _I64, [_P, _I32, _P, _I64, _P, _I64, _P, _I64]),
+    ("sc_schur_expand_host_multi", _I64, [_P, _I32, _P, _I64, _P, _I64, _P, _I64]),
     ("sc_etree", _I64, [_I64, _P, _P, _P]),
     ("sc_post_order", _I64, [_I64, _P, _P]),
     ("sc_col_count", _I64, [_I64, _P, _P, _P, _P, _P]),
@@ -171,6 +181,7 @@ _SIGS = [
     ("sc_debug_syrk_ex", _I64, [_P, _I32, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32]),
     ("sc_debug_panel", _I64, [_P, _I32, _I32, _I32, _I32, C.POINTER(_I32)]),
     ("sc_debug_updown_block", _I64, [_P, _I32, _I32, _I32, _P, _I32, C.POINTER(_I32)]),
+    ("sc_debug_schur_llt", _I64, [_P, _I32, _I64, _P, _I64]),
     ("sc_debug_bench", _I64, [_I32, _I32, _I32, _I32, _I32, C.POINTER(_D)]),
     ("sc_device_count", _I64, []),
     ("sc_debug_chain_stamps", _I64, [_P, _I32, _P, _I64]),
@@ -513,15 +524,29 @@ def _updown_W(W, n: int):
 
 
 class Symbolic:
-    """Host symbolic analysis (schol + supernodal plan)."""
+    """Host symbolic analysis (schol + supernodal plan).  ``schur=idx``: a Schur analysis
+    (sc_analyze_schur) that orders the distinct rows ``idx`` last, in the given order, for
+    :meth:`Numeric.schur_complement` and the partial solves."""
 
-    def __init__(self, A: csc_matrix, options: Optional[Options] = None, **kw):
+    def __init__(self, A: csc_matrix, options: Optional[Options] = None, schur=None, **kw):
         self.A = A
         self.opt = options if options is not None else default_options(**kw)
         h = C.c_void_p()
-        _check(lib().sc_analyze(A.size(), _ptr(A.p), _ptr(A.i), C.byref(self.opt), C.byref(h)), "analyze")
+        if schur is None:
+            _check(lib().sc_analyze(A.size(), _ptr(A.p), _ptr(A.i), C.byref(self.opt), C.byref(h)), "analyze")
+        else:
+            idx = np.ascontiguousarray(schur, dtype=np.int32).reshape(-1)
+            _check(lib().sc_analyze_schur(A.size(), _ptr(A.p), _ptr(A.i), C.byref(self.opt), len(idx),
+                                          _ptr(idx) if len(idx) else None, C.byref(h)), "analyze_schur")
         self.h = h
         self.n = A.size()
+
+    def schur_indices(self) -> np.ndarray:
+        """The index set of a Schur analysis in the caller's order (empty for a plain one)."""
+        ns = _check(lib().sc_symbolic_schur(self.h, None), "schur_indices")
+        idx = np.zeros(max(ns, 1), dtype=np.int32)
+        _check(lib().sc_symbolic_schur(self.h, _ptr(idx)), "schur_indices")
+        return idx[:ns]
 
     def stats(self) -> dict:
         st = SymbolicStats()
@@ -907,6 +932,78 @@ class Numeric:
     def downdate(self, W) -> int:
         """A <- A - W W^T (:meth:`updown` with sign -1)."""
         return self.updown(W, -1)
+
+    def _schur_dense(self, fn, what: str) -> np.ndarray:
+        ns = len(self.symb.schur_indices())
+        out = np.zeros((ns, ns), dtype=np.float64, order="F")
+        st = _check(fn(self.h, _ptr(out), max(ns, 1)), what)
+        if st > 0:
+            raise LibraryError(f"{what}: A is not positive definite (column {st})")
+        return out
+
+    def schur_factor(self) -> np.ndarray:
+        """D = L_SS, the (ns, ns) lower-triangular trailing block of L of a Schur analysis, row
+        and column q standing for ``schur_indices()[q]``; S_c = D D^T (sc_schur_factor_host)."""
+        return self._schur_dense(lib().sc_schur_factor_host, "schur_factor")
+
+    def schur_complement(self) -> np.ndarray:
+        """S_c = A_SS - A_SI inv(A_II) A_IS, (ns, ns), exactly symmetric, numbered as
+        ``schur_indices()`` (sc_schur_matrix_host)."""
+        return self._schur_dense(lib().sc_schur_matrix_host, "schur_complement")
+
+    def schur_factor_device(self, d_D_ptr: int, ldd: int) -> int:
+        """:meth:`schur_factor` into device memory, column-major with leading dimension ldd >= ns."""
+        return _check(lib().sc_schur_factor_device(self.h, C.c_void_p(d_D_ptr), ldd), "schur_factor_device")
+
+    def schur_complement_device(self, d_S_ptr: int, lds: int) -> int:
+        """:meth:`schur_complement` into device memory, column-major with leading dimension lds >= ns."""
+        return _check(lib().sc_schur_matrix_device(self.h, C.c_void_p(d_S_ptr), lds), "schur_complement_device")
+
+    def schur_condense(self, B: np.ndarray) -> np.ndarray:
+        """G = B_S - A_SI inv(A_II) B_I, the right-hand side of the interface problem S_c X_S = G.
+        B of shape (n,) or (n, k) in A's own order; G of shape (ns,) or (ns, k) in the order
+        of ``schur_indices()`` (sc_schur_condense_host_multi)."""
+        one = np.ndim(B) == 1
+        Bf = np.asfortranarray(np.asarray(B, dtype=np.float64).reshape(len(B), -1))
+        n, k = Bf.shape
+        if n != self.symb.n:
+            raise ValueError(f"schur_condense: B has {n} rows, the matrix {self.symb.n}")
+        ns = len(self.symb.schur_indices())
+        G = np.zeros((ns, k), dtype=np.float64, order="F")
+        st = _check(lib().sc_schur_condense_host_multi(self.h, k, _ptr(Bf), max(n, 1), _ptr(G), max(ns, 1)),
+                    "schur_condense")
+        if st > 0:
+            raise LibraryError(f"schur_condense: A is not positive definite (column {st})")
+        return G[:, 0].copy() if one else G
+
+    def schur_expand(self, B: np.ndarray, XS: np.ndarray) -> np.ndarray:
+        """X with X_S = XS (bit for bit) and X_I = inv(A_II) (B_I - A_IS XS): the solution of
+        A X = B when XS solves S_c XS = :meth:`schur_condense` (B).  B (n,) or (n, k), XS (ns,)
+        or (ns, k) (sc_schur_expand_host_multi)."""
+        one = np.ndim(B) == 1
+        Bf = np.asfortranarray(np.asarray(B, dtype=np.float64).reshape(len(B), -1))
+        n, k = Bf.shape
+        ns = len(self.symb.schur_indices())
+        Xs = np.asfortranarray(np.asarray(XS, dtype=np.float64).reshape(ns, -1))
+        if n != self.symb.n or Xs.shape[1] != k:
+            raise ValueError(f"schur_expand: B is {Bf.shape}, XS {Xs.shape}, the matrix has {self.symb.n} rows")
+        X = np.zeros((n, k), dtype=np.float64, order="F")
+        st = _check(lib().sc_schur_expand_host_multi(self.h, k, _ptr(Bf), max(n, 1), _ptr(Xs), max(ns, 1), _ptr(X),
+                                                     max(n, 1)), "schur_expand")
+        if st > 0:
+            raise LibraryError(f"schur_expand: A is not positive definite (column {st})")
+        return X[:, 0].copy() if one else X
+
+    def schur_condense_device_multi(self, d_B_ptr: int, nrhs: int, ldb: int, d_G_ptr: int, ldg: int) -> int:
+        """:meth:`schur_condense` with device arrays, column-major as for :meth:`solve_device_multi`."""
+        return _check(lib().sc_schur_condense_device_multi(self.h, nrhs, C.c_void_p(d_B_ptr), ldb, C.c_void_p(d_G_ptr),
+                                                           ldg), "schur_condense_device_multi")
+
+    def schur_expand_device_multi(self, d_B_ptr: int, nrhs: int, ldb: int, d_XS_ptr: int, ldxs: int, d_X_ptr: int,
+                                  ldx: int) -> int:
+        """:meth:`schur_expand` with device arrays (X may be B when ldx == ldb)."""
+        return _check(lib().sc_schur_expand_device_multi(self.h, nrhs, C.c_void_p(d_B_ptr), ldb, C.c_void_p(d_XS_ptr),
+                                                         ldxs, C.c_void_p(d_X_ptr), ldx), "schur_expand_device_multi")
 
     def selinv(self) -> int:
         """Selected inversion: every entry of A^-1 on the pattern of L into the handle's Z

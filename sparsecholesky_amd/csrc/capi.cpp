@@ -99,8 +99,10 @@ void sc_default_options(sc_options* opt) {
     opt->panel_prefactor = 1;
 }
 
-int64_t sc_analyze(int64_t n, const int64_t* Ap, const int32_t* Ai, const sc_options* opt,
-                   sc_symbolic** out) {
+// sc_analyze (ns == 0) and sc_analyze_schur (the list validated, ns > 0): the latter
+// factors P A P^T with the interior ordered by opt->ordering and schur_idx last.
+static int64_t analyze_impl(int64_t n, const int64_t* Ap, const int32_t* Ai, const sc_options* opt, int32_t ns,
+                            const int32_t* schur_idx, sc_symbolic** out) {
     if (!out) return SC_ERR_ARG;
     *out = nullptr;
     sc_options o;
@@ -132,7 +134,7 @@ int64_t sc_analyze(int64_t n, const int64_t* Ap, const int32_t* Ai, const sc_opt
         if (o.ordering != SC_ORDER_NATURAL && o.ordering != SC_ORDER_ND && o.ordering != SC_ORDER_AMD) {
             rc = SC_ERR_ARG;
             err = "sc_options.ordering must be SC_ORDER_NATURAL, SC_ORDER_ND or SC_ORDER_AMD";
-        } else if (o.ordering != SC_ORDER_NATURAL && n > 0 && Ap && (Ai || Ap[n] == 0)) {
+        } else if ((o.ordering != SC_ORDER_NATURAL || ns > 0) && n > 0 && Ap && (Ai || Ap[n] == 0)) {
             // factor B = P A P^T; numeric values still come from A's arrays (a_src remapped)
             std::vector<int32_t> perm((size_t)n);
             std::vector<int64_t> Bp, src;
@@ -145,8 +147,9 @@ int64_t sc_analyze(int64_t n, const int64_t* Ap, const int32_t* Ai, const sc_opt
                 if (Ai[p] < 0 || Ai[p] >= n) rc = SC_ERR_ARG;
             if (rc != SC_OK) err = "malformed CSC";
             if (rc == SC_OK) {
-                rc = o.ordering == SC_ORDER_AMD ? sc::amd_order(n, Ap, Ai, perm.data())
-                                                : sc::nd_order(n, Ap, Ai, perm.data());
+                rc = ns > 0 ? sc::schur_order(n, Ap, Ai, o.ordering, ns, schur_idx, perm.data())
+                     : o.ordering == SC_ORDER_AMD ? sc::amd_order(n, Ap, Ai, perm.data())
+                                                  : sc::nd_order(n, Ap, Ai, perm.data());
                 if (rc != SC_OK) err = "ordering failed";
             }
             if (rc == SC_OK) {
@@ -158,6 +161,7 @@ int64_t sc_analyze(int64_t n, const int64_t* Ap, const int32_t* Ai, const sc_opt
                 for (int64_t q = 0; q < S.nnzA_used; ++q) S.a_src[q] = src[S.a_src[q]];
                 S.nnzA_in = Ap[n];
                 S.perm = std::move(perm);
+                S.n_schur = ns;
             }
         } else {
             rc = sc::analyze(n, Ap, Ai, o, h->S, err);
@@ -173,6 +177,44 @@ int64_t sc_analyze(int64_t n, const int64_t* Ap, const int32_t* Ai, const sc_opt
     }
     *out = h;
     return SC_OK;
+}
+
+int64_t sc_analyze(int64_t n, const int64_t* Ap, const int32_t* Ai, const sc_options* opt,
+                   sc_symbolic** out) {
+    return analyze_impl(n, Ap, Ai, opt, 0, nullptr, out);
+}
+
+int64_t sc_analyze_schur(int64_t n, const int64_t* Ap, const int32_t* Ai, const sc_options* opt, int32_t ns,
+                         const int32_t* schur_idx, sc_symbolic** out) {
+    if (out) *out = nullptr;
+    auto fail = [&](const std::string& what) {
+        g_last_error = "sc_analyze_schur: " + what;
+        return (int64_t)SC_ERR_ARG;
+    };
+    if (ns < 0) return fail("ns = " + std::to_string(ns) + " < 0");
+    if (ns > n) return fail("ns = " + std::to_string(ns) + " exceeds n = " + std::to_string(n));
+    if (ns > 0 && !schur_idx) return fail("null schur_idx with ns = " + std::to_string(ns));
+    try {
+        std::vector<int32_t> at((size_t)std::max<int64_t>(n, 0), -1);  // position of an index in the list
+        for (int32_t q = 0; q < ns; ++q) {
+            const int32_t v = schur_idx[q];
+            const std::string name = "schur_idx[" + std::to_string(q) + "] = " + std::to_string(v);
+            if (v < 0 || v >= n) return fail(name + " is out of range [0, " + std::to_string(n) + ")");
+            if (at[v] >= 0) return fail(name + " appears twice (first as schur_idx[" + std::to_string(at[v]) + "])");
+            at[v] = q;
+        }
+    } catch (const std::bad_alloc&) {
+        return SC_ERR_NOMEM;
+    }
+    return analyze_impl(n, Ap, Ai, opt, ns, schur_idx, out);
+}
+
+int64_t sc_symbolic_schur(const sc_symbolic* sym, int32_t* schur_idx) {
+    if (!sym) return SC_ERR_ARG;
+    const auto& S = sym->S;
+    if (schur_idx && S.n_schur > 0)
+        std::memcpy(schur_idx, S.perm.data() + (S.n - S.n_schur), sizeof(int32_t) * (size_t)S.n_schur);
+    return S.n_schur;
 }
 
 int64_t sc_symbolic_get_stats(const sc_symbolic* sym, sc_symbolic_stats* st) {
@@ -632,6 +674,97 @@ int64_t sc_updown_host(sc_numeric* num, int32_t sign, int32_t k, const int64_t* 
     } catch (const std::bad_alloc&) {
         return SC_ERR_NOMEM;
     }
+}
+
+// ---- Schur complement ----
+static int64_t schur_out_args(sc_numeric* num, const void* out, int64_t ld, const char* who) {
+    const char* bad = nullptr;
+    if (!num || !num->N)
+        bad = "null handle";
+    else if (!out)
+        bad = "null output";
+    else if (ld < num->N->S->n_schur)
+        bad = "leading dimension below ns";
+    if (!bad) return SC_OK;
+    g_last_error = std::string(who) + ": " + bad;
+    return SC_ERR_ARG;
+}
+
+static int64_t schur_dense(sc_numeric* num, double* out, int64_t ld, bool matrix, bool host, const char* who) {
+    int64_t rc = schur_out_args(num, out, ld, who);
+    if (rc != SC_OK) return rc;
+    rc = matrix ? sc::numeric_schur_matrix(*num->N, out, ld, host) : sc::numeric_schur_factor(*num->N, out, ld, host);
+    if (rc < 0) g_last_error = num->N->err;
+    return rc;
+}
+
+int64_t sc_schur_factor_device(sc_numeric* num, double* d_D, int64_t ldd) {
+    return schur_dense(num, d_D, ldd, false, false, "sc_schur_factor_device");
+}
+int64_t sc_schur_factor_host(sc_numeric* num, double* D, int64_t ldd) {
+    return schur_dense(num, D, ldd, false, true, "sc_schur_factor_host");
+}
+int64_t sc_schur_matrix_device(sc_numeric* num, double* d_S, int64_t lds) {
+    return schur_dense(num, d_S, lds, true, false, "sc_schur_matrix_device");
+}
+int64_t sc_schur_matrix_host(sc_numeric* num, double* S, int64_t lds) {
+    return schur_dense(num, S, lds, true, true, "sc_schur_matrix_host");
+}
+
+// B / X by the rules of sc_apply_device_multi (has_x false: B alone), plus the ns-row array
+static int64_t schur_solve_args(sc_numeric* num, int32_t nrhs, const double* B, int64_t ldb, bool has_x, double* X,
+                                int64_t ldx, const double* GS, int64_t ldgs, const char* what, const char* who) {
+    int64_t rc = solve_multi_args(num, nrhs, B, ldb, has_x ? X : const_cast<double*>(B), has_x ? ldx : ldb, who);
+    if (rc != SC_OK) return rc;
+    const int64_t ns = num->N->S->n_schur;
+    const char* bad = nullptr;
+    if (ldgs < ns)
+        bad = " below ns";
+    else if (nrhs > 0 && ns > 0 && !GS)
+        bad = ": null array";
+    if (!bad) return SC_OK;
+    g_last_error = std::string(who) + ": " + what + bad;
+    return SC_ERR_ARG;
+}
+
+static int64_t schur_condense(sc_numeric* num, int32_t nrhs, const double* B, int64_t ldb, double* G, int64_t ldg,
+                              bool host, const char* who) {
+    int64_t rc = schur_solve_args(num, nrhs, B, ldb, false, nullptr, 0, G, ldg, "ldg / G", who);
+    if (rc != SC_OK) return rc;
+    rc = sc::numeric_schur_condense(*num->N, nrhs, B, ldb, G, ldg, host);
+    if (rc < 0) g_last_error = num->N->err;
+    return rc;
+}
+
+static int64_t schur_expand(sc_numeric* num, int32_t nrhs, const double* B, int64_t ldb, const double* XS,
+                            int64_t ldxs, double* X, int64_t ldx, bool host, const char* who) {
+    int64_t rc = schur_solve_args(num, nrhs, B, ldb, true, X, ldx, XS, ldxs, "ldxs / XS", who);
+    if (rc != SC_OK) return rc;
+    rc = sc::numeric_schur_expand(*num->N, nrhs, B, ldb, XS, ldxs, X, ldx, host);
+    if (rc < 0) g_last_error = num->N->err;
+    return rc;
+}
+
+int64_t sc_schur_condense_device_multi(sc_numeric* num, int32_t nrhs, const double* d_B, int64_t ldb, double* d_G,
+                                       int64_t ldg) {
+    return schur_condense(num, nrhs, d_B, ldb, d_G, ldg, false, "sc_schur_condense_device_multi");
+}
+int64_t sc_schur_condense_host_multi(sc_numeric* num, int32_t nrhs, const double* B, int64_t ldb, double* G,
+                                     int64_t ldg) {
+    return schur_condense(num, nrhs, B, ldb, G, ldg, true, "sc_schur_condense_host_multi");
+}
+int64_t sc_schur_expand_device_multi(sc_numeric* num, int32_t nrhs, const double* d_B, int64_t ldb,
+                                     const double* d_XS, int64_t ldxs, double* d_X, int64_t ldx) {
+    return schur_expand(num, nrhs, d_B, ldb, d_XS, ldxs, d_X, ldx, false, "sc_schur_expand_device_multi");
+}
+int64_t sc_schur_expand_host_multi(sc_numeric* num, int32_t nrhs, const double* B, int64_t ldb, const double* XS,
+                                   int64_t ldxs, double* X, int64_t ldx) {
+    return schur_expand(num, nrhs, B, ldb, XS, ldxs, X, ldx, true, "sc_schur_expand_host_multi");
+}
+
+int64_t sc_debug_schur_llt(const double* dD, int32_t ns, int64_t ldd, double* dS, int64_t lds) {
+    if (ns < 0 || ldd < ns || lds < ns || (ns > 0 && (!dD || !dS))) return SC_ERR_ARG;
+    return sc::debug_schur_llt(dD, ns, ldd, dS, lds);
 }
 
 // ---- reference-API helpers ----

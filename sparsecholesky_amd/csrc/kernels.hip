@@ -3605,4 +3605,173 @@ hipError_t launch_selinv_diag(const SelPlan& P, int ns, int64_t n, const int32_t
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------
+// Schur complement of an index set ordered last (schur.cpp).
+// P A P^T = L L^T with the caller's set S as the last ns rows: L_SS = D is the trailing
+// block of L, S_c = A_SS - A_SI inv(A_II) A_IS = D D^T.
+//
+// Gather.  Schur column q is column j = n - ns + q of P A P^T; in the internal (postorder)
+// numbering it sits in supernode cols[q].x at local column cols[q].y.  The Schur columns are
+// an ancestor-closed set of the etree, but a postorder may interleave them with interior
+// subtrees and relaxed amalgamation may merge interior and Schur columns into one supernode,
+// so every front row is mapped back on its own and kept only when its row i of P A P^T is
+// >= j: the others are relaxed zeros.  Only front rows r >= c are read, never the strict
+// upper triangle of a diagonal block (the solves' stored inverses).
+//
+// Product.  One workgroup (four waves) per 64 x 64 tile (I >= J) of the lower triangle on
+// the tile body of the selected inversion (sel_mma: K staged SEL_BK deep through LDS, the next
+// round's loads in flight under the products), K ascending over [0, min(ns, 64 (J + 1))):
+// D(j, k) = 0 for k > j, so deeper K adds nothing.  Both operand functors return 0 above the
+// diagonal of D without using what is stored there.  The tile goes through LDS and leaves as
+// 64-double runs along the columns of S, for the mirrored tile too, both from the one computed
+// value (a diagonal tile takes its upper half from its lower half).
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void schur_gather_kernel(SchurPlan P, double* __restrict__ D, int64_t ldd) {
+    const int q = blockIdx.x;
+    const int2 sc = P.cols[q];
+    const int s = sc.x, c = sc.y, m = P.sn_m[s];
+    const int32_t* __restrict__ rows = P.rows + P.rows_ptr[s];
+    const double* __restrict__ col = P.panel_pool + P.panel_off[s] + (int64_t)c * m;
+    const int base = P.n - P.ns, j = base + q;
+    for (int r = c + (int)threadIdx.x; r < m; r += 256) {
+        const int i = P.post[rows[r]];
+        if (i >= j) D[(int64_t)q * ldd + (i - base)] = col[r];
+    }
+}
+
+__global__ __launch_bounds__(256) void schur_llt_kernel(const double* __restrict__ D, int ns, int64_t ldd,
+                                                        double* __restrict__ S, int64_t lds) {
+    __shared__ double As[SEL_BK * (SCHUR_BT + 16)], Bs[SEL_BK * (SCHUR_BT + 16)];
+    __shared__ double Ts[SCHUR_BT * (SCHUR_BT + 1)];
+    // tile (I, J), J <= I: block b = I (I + 1) / 2 + J
+    const int64_t b = blockIdx.x;
+    int I = (int)((sqrt(8.0 * (double)b + 1.0) - 1.0) * 0.5);
+    while ((int64_t)(I + 1) * (I + 2) / 2 <= b) ++I;
+    while ((int64_t)I * (I + 1) / 2 > b) --I;
+    const int J = (int)(b - (int64_t)I * (I + 1) / 2);
+    const int row0 = SCHUR_BT * I, col0 = SCHUR_BT * J;
+    double4_t acc[4];
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt) acc[nt] = double4_t {0.0, 0.0, 0.0, 0.0};
+    sel_mma<SCHUR_BT / 16, SCHUR_BT / 16, false, false>(
+        ns, ns - col0, min(ns, col0 + SCHUR_BT), row0,
+        [&](int i, int k) { return k <= i ? D[(int64_t)k * ldd + i] : 0.0; },
+        [&](int k, int j) { return k <= col0 + j ? D[(int64_t)k * ldd + col0 + j] : 0.0; }, acc, As, Bs);
+    const int tid = threadIdx.x, lane = tid & 63, wv = wave_id();
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+            Ts[(16 * nt + (lane & 15)) * (SCHUR_BT + 1) + 16 * wv + MFMA_F64_ROW(lane, r)] = acc[nt][r];
+    __syncthreads();
+    const bool diag = I == J;
+#pragma unroll 4
+    for (int q = 0; q < SCHUR_BT * SCHUR_BT / 256; ++q) {
+        const int e = tid + 256 * q, il = e & 63, jl = e >> 6;
+        if (row0 + il < ns && col0 + jl < ns)  // the lower triangle decides both: an exactly symmetric S
+            S[(int64_t)(col0 + jl) * lds + row0 + il] =
+                (diag && jl > il) ? Ts[il * (SCHUR_BT + 1) + jl] : Ts[jl * (SCHUR_BT + 1) + il];
+    }
+    if (diag) return;
+#pragma unroll 4
+    for (int q = 0; q < SCHUR_BT * SCHUR_BT / 256; ++q) {  // the mirrored tile: runs along its columns too
+        const int e = tid + 256 * q, jl = e & 63, il = e >> 6;
+        if (row0 + il < ns && col0 + jl < ns)
+            S[(int64_t)(row0 + il) * lds + col0 + jl] = Ts[jl * (SCHUR_BT + 1) + il];
+    }
+}
+
+// one thread per row i; k ascends to the workgroup's last row, rows above it sit out
+__global__ __launch_bounds__(64) void schur_mul_kernel(const double* __restrict__ D, int ns, int64_t ldd, int nr,
+                                                       const double* __restrict__ Y, int64_t ldy,
+                                                       double* __restrict__ G, int64_t ldg) {
+    const int i = (int)blockIdx.x * 64 + (int)threadIdx.x;
+    const int kend = min(ns, (int)blockIdx.x * 64 + 64);
+    double acc[SCHUR_RHS];
+#pragma unroll
+    for (int c = 0; c < SCHUR_RHS; ++c) acc[c] = 0.0;
+    for (int k = 0; k < kend; ++k) {
+        if (i >= ns || k > i) continue;
+        const double d = D[(int64_t)k * ldd + i];
+#pragma unroll
+        for (int c = 0; c < SCHUR_RHS; ++c)
+            if (c < nr) acc[c] = fma(d, Y[(int64_t)c * ldy + k], acc[c]);
+    }
+    if (i >= ns) return;
+#pragma unroll
+    for (int c = 0; c < SCHUR_RHS; ++c)
+        if (c < nr) G[(int64_t)c * ldg + i] = acc[c];
+}
+
+// one wave per row k of T = D^T X: lane l sums i = k + l, k + l + 64, ..; thread c adds the
+// 64 lane sums of column c in lane order
+__global__ __launch_bounds__(64) void schur_mul_t_kernel(const double* __restrict__ D, int ns, int64_t ldd, int nr,
+                                                         const double* __restrict__ X, int64_t ldx,
+                                                         double* __restrict__ T, int64_t ldt) {
+    __shared__ double red[SCHUR_RHS * 65];
+    const int k = blockIdx.x, lane = threadIdx.x;
+    double acc[SCHUR_RHS];
+#pragma unroll
+    for (int c = 0; c < SCHUR_RHS; ++c) acc[c] = 0.0;
+    for (int i = k + lane; i < ns; i += 64) {
+        const double d = D[(int64_t)k * ldd + i];
+#pragma unroll
+        for (int c = 0; c < SCHUR_RHS; ++c)
+            if (c < nr) acc[c] = fma(d, X[(int64_t)c * ldx + i], acc[c]);
+    }
+#pragma unroll
+    for (int c = 0; c < SCHUR_RHS; ++c) red[c * 65 + lane] = acc[c];
+    __syncthreads();
+    if (lane < nr) {
+        double v = 0.0;
+        for (int l = 0; l < 64; ++l) v += red[lane * 65 + l];
+        T[(int64_t)lane * ldt + k] = v;
+    }
+}
+
+__global__ __launch_bounds__(256) void schur_scatter_kernel(const int32_t* __restrict__ idx, int ns, int nr,
+                                                            const double* __restrict__ XS, int64_t ldxs,
+                                                            double* __restrict__ X, int64_t ldx) {
+    const int q = (int)blockIdx.x * 256 + (int)threadIdx.x;
+    if (q >= ns) return;
+    const int64_t row = idx[q];
+    for (int c = 0; c < nr; ++c) X[(int64_t)c * ldx + row] = XS[(int64_t)c * ldxs + q];
+}
+
+hipError_t launch_schur_gather(const SchurPlan& P, double* D, int64_t ldd, hipStream_t st) {
+    if (P.ns <= 0) return hipSuccess;
+    hipLaunchKernelGGL(schur_gather_kernel, dim3((unsigned)P.ns), dim3(256), 0, st, P, D, ldd);
+    return hipGetLastError();
+}
+
+hipError_t launch_schur_llt(const double* D, int ns, int64_t ldd, double* S, int64_t lds, hipStream_t st) {
+    if (ns <= 0) return hipSuccess;
+    const int64_t T = (ns + SCHUR_BT - 1) / SCHUR_BT;
+    hipLaunchKernelGGL(schur_llt_kernel, dim3((unsigned)(T * (T + 1) / 2)), dim3(256), 0, st, D, ns, ldd, S, lds);
+    return hipGetLastError();
+}
+
+hipError_t launch_schur_mul(const double* D, int ns, int nr, const double* Y, int64_t ldy, double* G, int64_t ldg,
+                            hipStream_t st) {
+    if (ns <= 0 || nr <= 0) return hipSuccess;
+    hipLaunchKernelGGL(schur_mul_kernel, dim3((unsigned)((ns + 63) / 64)), dim3(64), 0, st, D, ns, (int64_t)ns, nr, Y,
+                       ldy, G, ldg);
+    return hipGetLastError();
+}
+
+hipError_t launch_schur_mul_t(const double* D, int ns, int nr, const double* X, int64_t ldx, double* T, int64_t ldt,
+                              hipStream_t st) {
+    if (ns <= 0 || nr <= 0) return hipSuccess;
+    hipLaunchKernelGGL(schur_mul_t_kernel, dim3((unsigned)ns), dim3(64), 0, st, D, ns, (int64_t)ns, nr, X, ldx, T, ldt);
+    return hipGetLastError();
+}
+
+hipError_t launch_schur_scatter(const int32_t* idx, int ns, int nr, const double* XS, int64_t ldxs, double* X,
+                                int64_t ldx, hipStream_t st) {
+    if (ns <= 0 || nr <= 0) return hipSuccess;
+    hipLaunchKernelGGL(schur_scatter_kernel, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, st, idx, ns, nr, XS, ldxs,
+                       X, ldx);
+    return hipGetLastError();
+}
+
 }  // namespace sc

@@ -270,6 +270,41 @@ hipError_t launch_updown_block(const UpdPlan& P, int s, int k0, int sign, hipStr
 // to wd through the front's row list; a wave loads its 16 rows whole before it stores.
 hipError_t launch_updown_rows(const UpdPlan& P, int s, int k0, int nr, hipStream_t st);
 
+// ---- Schur complement of an index set ordered last (schur.cpp) ----
+// The last ns columns of P A P^T are the caller's set: L_SS, their trailing block of L, is
+// gathered into a dense lower triangle D, and S_c = D D^T.
+struct SchurPlan {
+    const int32_t* sn_m;
+    const int64_t* panel_off;
+    const int64_t* rows_ptr;
+    const int32_t* rows;      // front rows (internal numbering)
+    const int32_t* post;      // internal -> row of P A P^T
+    const double* panel_pool;
+    const int2* cols;         // per Schur column q: (supernode, local column) of column n - ns + q
+    int32_t n, ns;
+};
+constexpr int SCHUR_BT = 64;   // tile edge of the product (four waves, 16 rows each)
+constexpr int SCHUR_RHS = 16;  // columns per panel of the partial solves (SOLVE_RHS)
+// D(i - (n - ns), q) = L(i, n - ns + q) for the front rows r >= c of column q whose row i of
+// P A P^T is >= the column; D (ld = ldd) was zero-filled by the caller.  One workgroup per
+// column: Schur columns need not be contiguous in the internal numbering, nor a supernode's
+// suffix.
+hipError_t launch_schur_gather(const SchurPlan& P, double* D, int64_t ldd, hipStream_t st);
+// S = D D^T for the lower triangle of D (ns x ns, column-major; what lies above its diagonal
+// is never used), both triangles of S from one computed value.  One workgroup per 64 x 64
+// tile (I >= J) of the lower triangle, K ascending over [0, min(ns, 64 (J + 1))) on
+// v_mfma_f64_16x16x4_f64; no atomics.  Nothing outside the ns x ns window of S is written.
+hipError_t launch_schur_llt(const double* D, int ns, int64_t ldd, double* S, int64_t lds, hipStream_t st);
+// G = D Y (ns x nr, nr <= SCHUR_RHS; column c of Y at Y + c ldy), one thread per row, k ascending.
+hipError_t launch_schur_mul(const double* D, int ns, int nr, const double* Y, int64_t ldy, double* G, int64_t ldg,
+                            hipStream_t st);
+// T = D^T X (ns x nr): one wave per row k of T, lanes over i >= k, lane sums added in lane order.
+hipError_t launch_schur_mul_t(const double* D, int ns, int nr, const double* X, int64_t ldx, double* T, int64_t ldt,
+                              hipStream_t st);
+// X(idx[q], c) = XS(q, c) for q < ns, c < nr
+hipError_t launch_schur_scatter(const int32_t* idx, int ns, int nr, const double* XS, int64_t ldxs, double* X,
+                                int64_t ldx, hipStream_t st);
+
 // Small fronts (m <= maxm <= 128): one workgroup per front, factored in registers
 // (4 x 4 tiles per thread); seq: one workgroup runs the fronts in order (a whole
 // small tree in postorder, CBs through HBM).

@@ -385,6 +385,17 @@ struct Numeric {
     double* d_uval = nullptr;
     int64_t upd_cap = 0;               // entries d_uidx / d_uval hold
 
+    // Schur complement (schur.cpp; single-device handles of a Schur analysis): D = L_SS
+    // (ns x ns, ld = ns), gathered once per generation of the factor, the per-column
+    // (supernode, local column) table and the index set, allocated at the first use; the
+    // n x SCHUR_RHS panel of the partial solves at the first of those
+    bool sch_ready = false;
+    SchurPlan SCH {};
+    double* d_schD = nullptr;
+    int32_t* d_schidx = nullptr;
+    int64_t sch_gen = -1;              // factor_gen the gathered D belongs to
+    double* d_schW = nullptr;
+
     std::string err;
 };
 
@@ -477,6 +488,19 @@ int64_t updown_check(const Symbolic& S, int32_t k, const int64_t* Wp, const int3
 // handle's status until the next factorization).
 int64_t numeric_updown_host(Numeric& N, int32_t sign, int32_t k, const int64_t* Wp, const int32_t* Wi,
                             const double* Wx);
+// Schur complement of the index set a Schur analysis ordered last (schur.cpp, DESIGN.md
+// section 9.4): D = L_SS and S_c = D D^T, ns x ns column-major in the caller's numbering
+// (row / column q is schur_idx[q]), and the two partial solves around S_c (B, X: n x nrhs in
+// A's order; G, XS: ns x nrhs).  Synchronous on the handle's stream; status rules of the
+// selected inversion; a handle without a Schur set: SC_OK, nothing touched (expand: the solve).
+int64_t numeric_schur_factor(Numeric& N, double* D, int64_t ldd, bool host);
+int64_t numeric_schur_matrix(Numeric& N, double* S, int64_t lds, bool host);
+int64_t numeric_schur_condense(Numeric& N, int32_t nrhs, const double* B, int64_t ldb, double* G, int64_t ldg,
+                               bool host);
+int64_t numeric_schur_expand(Numeric& N, int32_t nrhs, const double* B, int64_t ldb, const double* XS, int64_t ldxs,
+                             double* X, int64_t ldx, bool host);
+// The product kernel alone on caller data (device), synchronous.
+int64_t debug_schur_llt(const double* dD, int32_t ns, int64_t ldd, double* dS, int64_t lds);
 // The two kernels of one block step on block k0 of a caller's m x w panel and m x UPD_W
 // workspace (device; dW row-major, row = front row), through a one-front plan.
 int64_t debug_updown_block(double* dF, int m, int w, int k0, double* dW, int sign, int32_t* info);

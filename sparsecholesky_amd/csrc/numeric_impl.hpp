@@ -102,6 +102,9 @@ SchedDigest schedule_digest(const Numeric& N, const SchedBuild& B);
 // solve.cpp
 // What every solve starts with: the whole factor in gpanel, the solve plan built.
 int64_t solve_prepare(Numeric& N);
+// solve_prepare plus the etree postorder alone on the device (N.d_etpost), which the factor
+// operators and the Schur gather address rows of P A P^T by.
+int64_t apply_prepare(Numeric& N);
 // The diagonal-block inverses of the current factorization in place (launch_solve_inv,
 // once per factorization; shared by the solves, the half solves and the selected inversion).
 int64_t solve_inverses(Numeric& N);

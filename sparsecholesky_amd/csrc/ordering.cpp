@@ -494,6 +494,42 @@ i64 amd_order(i64 n, const i64* Ap, const i32* Ai, i32* perm) {
     return SC_OK;
 }
 
+// The interior keeps its ascending order in the induced matrix, so an upper entry of A
+// between two interior indices is an upper entry of A_II.  The induced graph may be
+// disconnected (S is typically a separator) or empty; nd_order numbers components one by
+// one and amd_order makes an element without variables a root, so both cope.
+i64 schur_order(i64 n, const i64* Ap, const i32* Ai, i32 ordering, i32 ns, const i32* schur_idx, i32* perm) {
+    const i64 ni = n - ns;
+    std::vector<i32> local((size_t)n, 0);  // old -> index in the interior, -1 for a Schur index
+    for (i32 q = 0; q < ns; ++q) local[schur_idx[q]] = -1;
+    std::vector<i32> interior;
+    interior.reserve((size_t)ni);
+    for (i64 v = 0; v < n; ++v)
+        if (local[v] == 0) {
+            local[v] = (i32)interior.size();
+            interior.push_back((i32)v);
+        }
+    for (i32 q = 0; q < ns; ++q) perm[ni + q] = schur_idx[q];
+    if (ordering == SC_ORDER_NATURAL || ni == 0) {
+        for (i64 q = 0; q < ni; ++q) perm[q] = interior[q];
+        return SC_OK;
+    }
+    std::vector<i64> Bp((size_t)ni + 1, 0);
+    std::vector<i32> Bi;
+    for (i64 q = 0; q < ni; ++q) {
+        const i64 k = interior[q];
+        for (i64 p = Ap[k]; p < Ap[k + 1]; ++p)
+            if (Ai[p] <= k && local[Ai[p]] >= 0) Bi.push_back(local[Ai[p]]);
+        Bp[q + 1] = (i64)Bi.size();
+    }
+    std::vector<i32> lperm((size_t)ni);
+    const i64 rc = ordering == SC_ORDER_AMD ? amd_order(ni, Bp.data(), Bi.data(), lperm.data())
+                                            : nd_order(ni, Bp.data(), Bi.data(), lperm.data());
+    if (rc != SC_OK) return rc;
+    for (i64 q = 0; q < ni; ++q) perm[q] = interior[lperm[q]];
+    return SC_OK;
+}
+
 // B = P A P^T as upper CSC (rows ascending; duplicates kept in input order so the
 // reference's last-one-wins rule still applies), src[q] = index of B's entry q in
 // A's arrays.  iperm[old] = new.

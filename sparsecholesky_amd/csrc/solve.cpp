@@ -394,7 +394,7 @@ int64_t numeric_solve_host_multi(Numeric& N, int32_t nrhs, const double* B, int6
 // gather by one of the two index arrays and a scatter by the other:
 //   P:   c[i] = b[perm[post[i]]],  x[post[i]] = c[i]        =>  x[k] = b[perm[k]]
 //   P^T: c[i] = b[post[i]],        x[perm[post[i]]] = c[i]  =>  x[perm[k]] = b[k]
-static int64_t apply_prepare(Numeric& N) {
+int64_t apply_prepare(Numeric& N) {
     TRY(solve_prepare(N));
     if (!N.d_etpost) {
         if (N.S->perm.empty())

@@ -51,6 +51,7 @@ struct Symbolic {
 
     // natural-order symbolic (reference semantics)
     std::vector<i32> perm;      // fill-reducing ordering, new -> old (empty: the given order)
+    i32 n_schur = 0;            // Schur handle: the last n_schur entries of perm are the caller's index set
     std::vector<i32> parent;    // etree
     std::vector<i32> post;      // internal -> natural
     std::vector<i32> ipost;     // natural -> internal
@@ -109,6 +110,12 @@ i64 analyze(i64 n, const i64* Ap, const i32* Ai, const sc_options& opt, Symbolic
 i64 nd_order(i64 n, const i64* Ap, const i32* Ai, i32* perm);
 // Approximate minimum degree ordering (ordering.cpp), perm[new] = old.
 i64 amd_order(i64 n, const i64* Ap, const i32* Ai, i32* perm);
+// Constrained ordering of a Schur analysis (ordering.cpp): the interior (every index not
+// in schur_idx) first, ordered by `ordering` (sc_options.ordering) on the induced graph
+// A_II -- natural: ascending; ND / AMD: nd_order / amd_order of the induced upper CSC,
+// mapped back -- then schur_idx in the given order.  The list must be valid (distinct,
+// in range) and the CSC well formed.  perm[new] = old.
+i64 schur_order(i64 n, const i64* Ap, const i32* Ai, i32 ordering, i32 ns, const i32* schur_idx, i32* perm);
 void permute_upper(i64 n, const i64* Ap, const i32* Ai, const i32* perm, std::vector<i64>& Bp,
                    std::vector<i32>& Bi, std::vector<i64>& src);
 
