@@ -34,7 +34,7 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define SC_VERSION 121 /* still 1.2.1, additive: Schur complement sc_analyze_schur / sc_symbolic_schur / sc_schur_factor_* / sc_schur_matrix_* / sc_schur_condense_*_multi / sc_schur_expand_*_multi; still 1.2.1, additive: rank-k update / downdate sc_updown_check / sc_updown_host; still 1.2.1, additive: selected inversion sc_selinv / sc_selinv_diag_host / sc_selinv_diag_device / sc_selinv_export / sc_selinv_flops; still 1.2.1, additive: the factor operators sc_apply_host / sc_apply_device / sc_apply_host_multi / sc_apply_device_multi (enum sc_factor_op) and sc_logdet; still 1.2.1, additive: sc_solve_host_multi / sc_solve_device_multi (nrhs right-hand sides); 1.2.1:small merged fronts amalgamated past relax_wmax (different supernode partition of some inputs, same L); 1.2.0: persistent slab chain options removed; panel_prefactor, dist_local_pieces and SC_ORDER_AMD added; out-of-range lookahead / inner_order / ordering rejected */
+#define SC_VERSION 121 /* still 1.2.1, additive: products with A, residuals and iterative refinement sc_spmv_structure / sc_spmv_*_multi / sc_residual_*_multi / sc_solve_refine_*_multi / sc_default_refine_options; still 1.2.1, additive: Schur complement sc_analyze_schur / sc_symbolic_schur / sc_schur_factor_* / sc_schur_matrix_* / sc_schur_condense_*_multi / sc_schur_expand_*_multi; still 1.2.1, additive: rank-k update / downdate sc_updown_check / sc_updown_host; still 1.2.1, additive: selected inversion sc_selinv / sc_selinv_diag_host / sc_selinv_diag_device / sc_selinv_export / sc_selinv_flops; still 1.2.1, additive: the factor operators sc_apply_host / sc_apply_device / sc_apply_host_multi / sc_apply_device_multi (enum sc_factor_op) and sc_logdet; still 1.2.1, additive: sc_solve_host_multi / sc_solve_device_multi (nrhs right-hand sides); 1.2.1:small merged fronts amalgamated past relax_wmax (different supernode partition of some inputs, same L); 1.2.0: persistent slab chain options removed; panel_prefactor, dist_local_pieces and SC_ORDER_AMD added; out-of-range lookahead / inner_order / ordering rejected */
 
 enum sc_status {
     SC_OK = 0,
@@ -501,6 +501,100 @@ int64_t sc_schur_expand_device_multi(sc_numeric* num, int32_t nrhs, const double
                                      const double* d_XS, int64_t ldxs, double* d_X, int64_t ldx);
 int64_t sc_schur_expand_host_multi(sc_numeric* num, int32_t nrhs, const double* B, int64_t ldb, const double* XS,
                                    int64_t ldxs, double* X, int64_t ldx);
+
+/* Products with A, residuals with backward errors, and iterative refinement on the GPU (what
+ * CHOLMOD, MUMPS, PARDISO and cuDSS users know as refinement steps and LAPACK's as xPORFS /
+ * xPOSVXX): how good a solution is, and a better one.
+ *   sc_spmv_*_multi          Y = A X
+ *   sc_residual_*_multi      R = B - A X with, per column, the normwise backward error
+ *                            berr_norm = |r|_inf / (|A|_inf |x|_inf + |b|_inf) and the componentwise
+ *                            one (Oettli-Prager) berr_comp = max_i |r_i| / (|b| + |A| |x|)_i, where
+ *                            0 / 0 counts as 0 and nonzero / 0 as +inf; both are host arrays of
+ *                            nrhs entries in the _device form too, and either may be NULL
+ *   sc_solve_refine_*_multi  X = A^-1 B by the panel solve and refinement steps
+ * A is the matrix the analysis saw: entries with row > column ignored, of duplicates of one
+ * (row, column) the last one, mirrored to the full symmetric matrix (sc_spmv_structure returns
+ * it by rows: rp[n + 1], ascending columns ci, and sp, the index of each value in the value
+ * array; two-phase like sc_triplet_to_csc: with ci == NULL it returns the entry count and
+ * fills rp if given; host only).  Numbering: every array is n x nrhs column-major in A's own
+ * order, whatever the ordering or the Schur set of the handle; leading dimensions >= n.
+ * Values: Ax (host forms) / d_Ax (device forms) has the length and order of Ai, exactly what
+ * sc_factor / sc_factor_device take, and is read where it lies.  NULL stands for the copy
+ * sc_factor made and is legal only when the handle's last factorization was an sc_factor
+ * (after sc_factor_device the library holds only a pointer of the caller's that it must not
+ * trust): SC_ERR_ARG with a message otherwise.  The values need not be the factored ones:
+ * the factor of A then serves a nearby A' as a preconditioner, each step costs one panel
+ * solve and contracts the error by rho(I - inv(A) A').  After sc_updown_host the factor
+ * describes A +- W W^T while Ax still describes A: refinement with those values converges to
+ * the solution of the Ax system if it converges at all.
+ * Residual precision: SC_RESIDUAL_FP64 accumulates b - sum a x with one fma per entry;
+ * SC_RESIDUAL_DD as a compensated dot product (Ogita, Rump, Oishi: Dot2), as if in twice the
+ * working precision, rounded to fp64 once -- which is what lets a refinement step return the
+ * correctly rounded solution of an ill-conditioned system.  |b| + |A| |x| is plain fp64.
+ * Refinement, per column, with d_k the k-th increment, |d_0| := |x_0|_inf, u = 2^-53:
+ *   x_0 = sc_solve_*_multi's result bit for bit (max_iter = 0 returns exactly that);
+ *   repeat: r = b - A x; d = solve(r);
+ *     DIVERGED   |d_k| >= |d_k-1| (or not a number): d_k is NOT applied, the column stops
+ *     otherwise x += d_k, iters += 1, and with the new x
+ *     CONVERGED  |d_k| <= u |x|; in FP64 mode also when berr_comp <= 2 u (xPORFS's rule)
+ *     STALLED    |d_k| > rho_max |d_k-1|
+ *     MAXITER    iters == max_iter
+ *   Before the first step a column whose residual is exactly zero (and in FP64 mode one
+ *   with berr_comp <= 2 u) is CONVERGED with iters = 0.
+ * A column that has stopped is frozen: later steps of its panel do not change a bit of it,
+ * and its result does not depend on the columns it travels with or on its position.
+ * sc_refine_info (nrhs entries, host memory, may be NULL) describes the returned X: iters,
+ * state, berr_norm, berr_comp (from one more residual pass after the last applied increment)
+ * and dx_ratio = |d_last| / |x| with d_last the last increment computed, applied or not.
+ * No atomics, fixed order: every result is bitwise repeatable across calls and handles.
+ * Status: refinement follows the solves -- SC_ERR_STATE before a factorization; a failed
+ * factorization returns its status > 0 and writes nothing; nrhs == 0 or n == 0: SC_OK.  The
+ * product and the residual never look at the factor and work, with explicit values, right
+ * after sc_numeric_create.  SC_ERR_ARG with the entry point's name in sc_last_error for a
+ * null handle or array, a leading dimension below n, nrhs < 0, an options struct of the
+ * wrong struct_size, max_iter < 0, rho_max outside (0, 1), an unknown residual mode, and for
+ * an output that is an input: refinement needs B after X exists, so in-place calls (X == B)
+ * are rejected, as are R == B, R == X and Y == X (partial overlaps are not detected and not
+ * allowed).  Multi-rank and emulated handles:
+ * SC_ERR_NOTIMPL with a message.  Calls are synchronous on the handle's stream.
+ * Device memory, counted in sc_numeric_memory info[0], allocated at the first of these calls
+ * and kept until sc_free_numeric (nz = entries of sc_spmv_structure, a task = a row or, of a
+ * row longer than 256 entries, one chunk of 256; every term at least one element):
+ *   8 (n + 1) + 12 nz            the structure
+ *   16 per task, 8 per row longer than 256, 512 per chunk of such a row
+ *   640 per 256 tasks and per 16 rows longer than 256 (both rounded up)    norm partials
+ *   2 x 128 n                    the transposed X panel and the R / D panel
+ *   8960                         norms
+ * plus, for refinement, what the first sc_solve_*_multi allocates.  The _host forms stage
+ * their arrays (and Ax when given) in device memory for the length of the call. */
+enum { SC_RESIDUAL_FP64 = 0, SC_RESIDUAL_DD = 1 };
+enum { SC_REFINE_CONVERGED = 0, SC_REFINE_STALLED = 1, SC_REFINE_MAXITER = 2, SC_REFINE_DIVERGED = 3 };
+typedef struct sc_refine_options {
+    int32_t struct_size; /* sizeof(sc_refine_options), set by sc_default_refine_options */
+    int32_t max_iter;    /* increments applied at most (10) */
+    int32_t residual;    /* SC_RESIDUAL_DD */
+    double rho_max;      /* 0.5, as in xGERFSX */
+} sc_refine_options;
+typedef struct sc_refine_info {
+    int32_t iters, state;
+    double berr_norm, berr_comp, dx_ratio;
+} sc_refine_info;
+void sc_default_refine_options(sc_refine_options* opt);
+int64_t sc_spmv_structure(const sc_symbolic* sym, int64_t* rp, int32_t* ci, int64_t* sp);
+int64_t sc_spmv_host_multi(sc_numeric* num, int32_t nrhs, const double* Ax, const double* X, int64_t ldx, double* Y,
+                           int64_t ldy);
+int64_t sc_spmv_device_multi(sc_numeric* num, int32_t nrhs, const double* d_Ax, const double* d_X, int64_t ldx,
+                             double* d_Y, int64_t ldy);
+int64_t sc_residual_host_multi(sc_numeric* num, int32_t residual, int32_t nrhs, const double* Ax, const double* B,
+                               int64_t ldb, const double* X, int64_t ldx, double* R, int64_t ldr, double* berr_norm,
+                               double* berr_comp);
+int64_t sc_residual_device_multi(sc_numeric* num, int32_t residual, int32_t nrhs, const double* d_Ax,
+                                 const double* d_B, int64_t ldb, const double* d_X, int64_t ldx, double* d_R,
+                                 int64_t ldr, double* berr_norm, double* berr_comp);
+int64_t sc_solve_refine_host_multi(sc_numeric* num, const sc_refine_options* opt, int32_t nrhs, const double* Ax,
+                                   const double* B, int64_t ldb, double* X, int64_t ldx, sc_refine_info* info);
+int64_t sc_solve_refine_device_multi(sc_numeric* num, const sc_refine_options* opt, int32_t nrhs, const double* d_Ax,
+                                     const double* d_B, int64_t ldb, double* d_X, int64_t ldx, sc_refine_info* info);
 
 /* ---------------- reference-API helpers (host) ----------------
  * Each mirrors one reference function, with int64 column pointers. */

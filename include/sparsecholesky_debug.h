@@ -69,6 +69,18 @@ int64_t sc_debug_selinv_cols(sc_numeric* num, int64_t j0, int64_t j1, int64_t* c
  * triangles of dS written; what dD holds above its diagonal is never used, nothing outside
  * the ns x ns window of dS is written.  Synchronous. */
 int64_t sc_debug_schur_llt(const double* dD, int32_t ns, int64_t ldd, double* dS, int64_t lds);
+/* The product / residual kernels alone (no handle) on a caller's row structure -- host
+ * arrays in the layout of sc_spmv_structure, validated before anything is launched: rp
+ * ascending from 0, ci in [0, n), sp in [0, nval) -- with values d_Ax (nval doubles) and
+ * panels in device memory: d_X, d_B, d_R, d_W are n x nrhs column-major (leading dimensions
+ * >= n, nrhs <= 16).  mode 0: R = A X (B, W, norms unused); 1 / 2: R = B - A X accumulated
+ * in fp64 / as a compensated dot product, W = |B| + |A| |X| (d_W may be NULL) and d_norms
+ * (may be NULL; 5 x 16 doubles, value q of column c at 16 q + c): max |r|, max |x|, max |b|,
+ * max |r| / w (0 / 0 = 0, nonzero / 0 = +inf), largest row sum of |A|; columns >= nrhs
+ * zero.  Nothing outside the n x nrhs windows is read or written.  Synchronous. */
+int64_t sc_debug_spmv(int32_t mode, int32_t n, const int64_t* rp, const int32_t* ci, const int64_t* sp, int64_t nval,
+                      const double* d_Ax, int32_t nrhs, const double* d_X, int64_t ldx, const double* d_B, int64_t ldb,
+                      double* d_R, int64_t ldr, double* d_W, int64_t ldw, double* d_norms);
 /* Chain launches (runs of single small-front levels): enable = 1 makes the next
  * eager factorizations record 8 shader-clock stamps per chained front (phase
  * boundaries); enable = 0 copies up to cap of them to out.  Returns the count. */

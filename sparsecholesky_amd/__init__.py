@@ -46,6 +46,8 @@ __all__ = [
     "csc_to_dense", "compute_levels", "compute_supernodes", "atree", "laplacian3d",
     "Symbolic", "Numeric", "Options",
     "SC_OP_SOLVE_A", "SC_OP_SOLVE_L", "SC_OP_SOLVE_LT", "SC_OP_MUL_L", "SC_OP_MUL_LT", "SC_OP_PERM", "SC_OP_PERM_T",
+    "RefineOptions", "RefineInfo", "SC_RESIDUAL_FP64", "SC_RESIDUAL_DD",
+    "SC_REFINE_CONVERGED", "SC_REFINE_STALLED", "SC_REFINE_MAXITER", "SC_REFINE_DIVERGED",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -54,6 +56,10 @@ LIB_PATH = os.path.join(_HERE, "libsparsecholesky_amd.so")
 SC_OK = 0
 # enum sc_factor_op: what Numeric.apply / sc_apply_* compute from the factor P A P^T = L L^T
 SC_OP_SOLVE_A, SC_OP_SOLVE_L, SC_OP_SOLVE_LT, SC_OP_MUL_L, SC_OP_MUL_LT, SC_OP_PERM, SC_OP_PERM_T = range(7)
+# residual accumulation of Numeric.residual / solve_refined, and the states a refined column ends in
+SC_RESIDUAL_FP64, SC_RESIDUAL_DD = 0, 1
+SC_REFINE_CONVERGED, SC_REFINE_STALLED, SC_REFINE_MAXITER, SC_REFINE_DIVERGED = range(4)
+_RESIDUAL_MODES = {"fp64": SC_RESIDUAL_FP64, "dd": SC_RESIDUAL_DD}
 _STATUS = {
     -1: "invalid argument", -2: "host allocation failed", -3: "HIP runtime error",
     -4: "device allocation failed", -5: "call out of order", -6: "communication error",
@@ -79,6 +85,16 @@ class Options(C.Structure):
         ("dist_asm", C.c_int32),
         ("dist_pieces", C.c_int32), ("dist_local_pieces", C.c_int32), ("panel_prefactor", C.c_int32),
     ]
+
+
+class RefineOptions(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("max_iter", C.c_int32), ("residual", C.c_int32),
+                ("rho_max", C.c_double)]
+
+
+class RefineInfo(C.Structure):
+    _fields_ = [("iters", C.c_int32), ("state", C.c_int32), ("berr_norm", C.c_double),
+                ("berr_comp", C.c_double), ("dx_ratio", C.c_double)]
 
 
 class SymbolicStats(C.Structure):
@@ -155,6 +171,14 @@ _SIGS = [
     ("sc_schur_condense_host_multi", _I64, [_P, _I32, _P, _I64, _P, _I64]),
     ("sc_schur_expand_device_multi", _I64, [_P, _I32, _P, _I64, _P, _I64, _P, _I64]),
     ("sc_schur_expand_host_multi", _I64, [_P, _I32, _P, _I64, _P, _I64, _P, _I64]),
+    ("sc_default_refine_options", None, [C.POINTER(RefineOptions)]),
+    ("sc_spmv_structure", _I64, [_P, _P, _P, _P]),
+    ("sc_spmv_host_multi", _I64, [_P, _I32, _P, _P, _I64, _P, _I64]),
+    ("sc_spmv_device_multi", _I64, [_P, _I32, _P, _P, _I64, _P, _I64]),
+    ("sc_residual_host_multi", _I64, [_P, _I32, _I32, _P, _P, _I64, _P, _I64, _P, _I64, _P, _P]),
+    ("sc_residual_device_multi", _I64, [_P, _I32, _I32, _P, _P, _I64, _P, _I64, _P, _I64, _P, _P]),
+    ("sc_solve_refine_host_multi", _I64, [_P, C.POINTER(RefineOptions), _I32, _P, _P, _I64, _P, _I64, _P]),
+    ("sc_solve_refine_device_multi", _I64, [_P, C.POINTER(RefineOptions), _I32, _P, _P, _I64, _P, _I64, _P]),
     ("sc_etree", _I64, [_I64, _P, _P, _P]),
     ("sc_post_order", _I64, [_I64, _P, _P]),
     ("sc_col_count", _I64, [_I64, _P, _P, _P, _P, _P]),
@@ -182,6 +206,7 @@ _SIGS = [
     ("sc_debug_panel", _I64, [_P, _I32, _I32, _I32, _I32, C.POINTER(_I32)]),
     ("sc_debug_updown_block", _I64, [_P, _I32, _I32, _I32, _P, _I32, C.POINTER(_I32)]),
     ("sc_debug_schur_llt", _I64, [_P, _I32, _I64, _P, _I64]),
+    ("sc_debug_spmv", _I64, [_I32, _I32, _P, _P, _P, _I64, _P, _I32, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _P]),
     ("sc_debug_bench", _I64, [_I32, _I32, _I32, _I32, _I32, C.POINTER(_D)]),
     ("sc_device_count", _I64, []),
     ("sc_debug_chain_stamps", _I64, [_P, _I32, _P, _I64]),
@@ -547,6 +572,18 @@ class Symbolic:
         idx = np.zeros(max(ns, 1), dtype=np.int32)
         _check(lib().sc_symbolic_schur(self.h, _ptr(idx)), "schur_indices")
         return idx[:ns]
+
+    def spmv_structure(self) -> tuple:
+        """The full symmetric A the analysis saw (entries with row > column ignored, of
+        duplicates the last one, mirrored), by rows in A's own numbering: (rp, ci, sp) with
+        ascending columns ci per row and sp the index of each value in the value array
+        (sc_spmv_structure).  Host only."""
+        rp = np.zeros(self.n + 1, dtype=np.int64)
+        nz = _check(lib().sc_spmv_structure(self.h, _ptr(rp), None, None), "spmv_structure")
+        ci = np.zeros(max(nz, 1), dtype=np.int32)
+        sp = np.zeros(max(nz, 1), dtype=np.int64)
+        assert _check(lib().sc_spmv_structure(self.h, _ptr(rp), _ptr(ci), _ptr(sp)), "spmv_structure") == nz
+        return rp, ci[:nz], sp[:nz]
 
     def stats(self) -> dict:
         st = SymbolicStats()
@@ -1004,6 +1041,106 @@ class Numeric:
         """:meth:`schur_expand` with device arrays (X may be B when ldx == ldb)."""
         return _check(lib().sc_schur_expand_device_multi(self.h, nrhs, C.c_void_p(d_B_ptr), ldb, C.c_void_p(d_XS_ptr),
                                                          ldxs, C.c_void_p(d_X_ptr), ldx), "schur_expand_device_multi")
+
+    def _panel_in(self, A: np.ndarray, what: str):
+        """(n,) or (n, k) host input as a Fortran (n, k) array, with whether it was 1-D."""
+        one = np.ndim(A) == 1
+        F = np.asfortranarray(np.reshape(A, (-1, 1)) if one else A, dtype=np.float64)
+        if F.ndim != 2 or F.shape[0] != self.symb.n:
+            raise ValueError(f"{what}: the array is {np.shape(A)}, the matrix has {self.symb.n} rows")
+        return F, one
+
+    @staticmethod
+    def _values(Ax):
+        return None if Ax is None else np.ascontiguousarray(Ax, dtype=np.float64)
+
+    def spmv(self, X: np.ndarray, Ax=None) -> np.ndarray:
+        """Y = A X on the GPU (host arrays; X (n,) or (n, k), returned in the same shape), A
+        being the matrix the analysis saw with the values ``Ax`` (the order :meth:`factor`
+        takes), or, with ``Ax=None``, the values of the last :meth:`factor`
+        (sc_spmv_host_multi)."""
+        Xf, one = self._panel_in(X, "spmv")
+        n, k = Xf.shape
+        Y = np.zeros((n, k), dtype=np.float64, order="F")
+        ld = max(n, 1)
+        _check(lib().sc_spmv_host_multi(self.h, k, _ptr(self._values(Ax)), _ptr(Xf), ld, _ptr(Y), ld), "spmv")
+        return Y[:, 0] if one else Y
+
+    def residual(self, B: np.ndarray, X: np.ndarray, Ax=None, mode: str = "dd") -> tuple:
+        """(R, berr_norm, berr_comp): R = B - A X with, per column, the normwise and the
+        componentwise (Oettli-Prager) backward error; ``mode`` "dd" accumulates the residual
+        as a compensated dot product, "fp64" in working precision (sc_residual_host_multi).
+        B and X (n,) or (n, k); the errors are arrays of k entries (floats for 1-D input)."""
+        Bf, one = self._panel_in(B, "residual")
+        Xf, _ = self._panel_in(X, "residual")
+        if Xf.shape != Bf.shape:
+            raise ValueError(f"residual: B is {Bf.shape}, X {Xf.shape}")
+        n, k = Bf.shape
+        R = np.zeros((n, k), dtype=np.float64, order="F")
+        bn, bc = np.zeros(max(k, 1)), np.zeros(max(k, 1))
+        ld = max(n, 1)
+        _check(lib().sc_residual_host_multi(self.h, _RESIDUAL_MODES[mode], k, _ptr(self._values(Ax)), _ptr(Bf), ld,
+                                            _ptr(Xf), ld, _ptr(R), ld, _ptr(bn), _ptr(bc)), "residual")
+        return (R[:, 0], float(bn[0]), float(bc[0])) if one else (R, bn[:k], bc[:k])
+
+    @staticmethod
+    def _refine_options(max_iter: int, residual: str, rho_max: float) -> RefineOptions:
+        o = RefineOptions()
+        lib().sc_default_refine_options(C.byref(o))
+        o.max_iter, o.residual, o.rho_max = max_iter, _RESIDUAL_MODES[residual], rho_max
+        return o
+
+    @staticmethod
+    def _refine_info(info, k: int, one: bool) -> dict:
+        d = {f: np.array([getattr(info[j], f) for j in range(k)]) for f, _ in RefineInfo._fields_}
+        return {f: v[0].item() for f, v in d.items()} if one else d
+
+    def solve_refined(self, B: np.ndarray, Ax=None, max_iter: int = 10, residual: str = "dd",
+                      rho_max: float = 0.5) -> tuple:
+        """(X, info): X = A^-1 B by the panel solve plus iterative refinement against the
+        values ``Ax`` (``None``: those of the last :meth:`factor`), the residual accumulated
+        as ``residual`` says ("dd": as if in twice the working precision).  ``info``: a dict
+        of arrays over the columns -- iters, state (SC_REFINE_*), berr_norm, berr_comp,
+        dx_ratio -- describing the returned X (scalars for 1-D input).  B (n,) or (n, k)
+        (sc_solve_refine_host_multi)."""
+        Bf, one = self._panel_in(B, "solve_refined")
+        n, k = Bf.shape
+        X = np.zeros((n, k), dtype=np.float64, order="F")
+        info = (RefineInfo * max(k, 1))()
+        o = self._refine_options(max_iter, residual, rho_max)
+        ld = max(n, 1)
+        st = _check(lib().sc_solve_refine_host_multi(self.h, C.byref(o), k, _ptr(self._values(Ax)), _ptr(Bf), ld,
+                                                     _ptr(X), ld, info), "solve_refined")
+        if st > 0:
+            raise LibraryError(f"solve_refined: A is not positive definite (column {st})")
+        return (X[:, 0] if one else X), self._refine_info(info, k, one)
+
+    def spmv_device_multi(self, d_Ax_ptr: int, d_X_ptr: int, nrhs: int, ldx: int, d_Y_ptr: int, ldy: int) -> int:
+        """:meth:`spmv` with device arrays, column-major as for :meth:`solve_device_multi`;
+        d_Ax_ptr 0: the values of the last :meth:`factor`."""
+        return _check(lib().sc_spmv_device_multi(self.h, nrhs, C.c_void_p(d_Ax_ptr or None), C.c_void_p(d_X_ptr), ldx,
+                                                 C.c_void_p(d_Y_ptr), ldy), "spmv_device_multi")
+
+    def residual_device_multi(self, d_Ax_ptr: int, d_B_ptr: int, nrhs: int, ldb: int, d_X_ptr: int, ldx: int,
+                              d_R_ptr: int, ldr: int, mode: str = "dd") -> tuple:
+        """:meth:`residual` with device arrays; returns (berr_norm, berr_comp), host arrays."""
+        bn, bc = np.zeros(max(nrhs, 1)), np.zeros(max(nrhs, 1))
+        _check(lib().sc_residual_device_multi(self.h, _RESIDUAL_MODES[mode], nrhs, C.c_void_p(d_Ax_ptr or None),
+                                              C.c_void_p(d_B_ptr), ldb, C.c_void_p(d_X_ptr), ldx, C.c_void_p(d_R_ptr),
+                                              ldr, _ptr(bn), _ptr(bc)), "residual_device_multi")
+        return bn[:nrhs], bc[:nrhs]
+
+    def solve_refined_device_multi(self, d_Ax_ptr: int, d_B_ptr: int, nrhs: int, ldb: int, d_X_ptr: int, ldx: int,
+                                   max_iter: int = 10, residual: str = "dd", rho_max: float = 0.5) -> dict:
+        """:meth:`solve_refined` with device arrays (X must not be B); returns the info dict."""
+        info = (RefineInfo * max(nrhs, 1))()
+        o = self._refine_options(max_iter, residual, rho_max)
+        st = _check(lib().sc_solve_refine_device_multi(self.h, C.byref(o), nrhs, C.c_void_p(d_Ax_ptr or None),
+                                                       C.c_void_p(d_B_ptr), ldb, C.c_void_p(d_X_ptr), ldx, info),
+                    "solve_refined_device_multi")
+        if st > 0:
+            raise LibraryError(f"solve_refined_device_multi: A is not positive definite (column {st})")
+        return self._refine_info(info, nrhs, False)
 
     def selinv(self) -> int:
         """Selected inversion: every entry of A^-1 on the pattern of L into the handle's Z

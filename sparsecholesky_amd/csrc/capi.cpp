@@ -4,6 +4,7 @@
 #include <algorithm>
 #include <chrono>
 #include <cstring>
+#include <initializer_list>
 #include <new>
 #include <string>
 #include <vector>
@@ -765,6 +766,171 @@ int64_t sc_schur_expand_host_multi(sc_numeric* num, int32_t nrhs, const double* 
 int64_t sc_debug_schur_llt(const double* dD, int32_t ns, int64_t ldd, double* dS, int64_t lds) {
     if (ns < 0 || ldd < ns || lds < ns || (ns > 0 && (!dD || !dS))) return SC_ERR_ARG;
     return sc::debug_schur_llt(dD, ns, ldd, dS, lds);
+}
+
+// ---- products with A, residuals, iterative refinement ----
+void sc_default_refine_options(sc_refine_options* opt) {
+    if (!opt) return;
+    std::memset(opt, 0, sizeof(*opt));
+    opt->struct_size = (int32_t)sizeof(sc_refine_options);
+    opt->max_iter = 10;
+    opt->residual = SC_RESIDUAL_DD;
+    opt->rho_max = 0.5;
+}
+
+int64_t sc_spmv_structure(const sc_symbolic* sym, int64_t* rp, int32_t* ci, int64_t* sp) {
+    if (!sym || ((ci == nullptr) != (sp == nullptr))) {
+        g_last_error = "sc_spmv_structure: null handle, or only one of ci and sp given";
+        return SC_ERR_ARG;
+    }
+    try {
+        return sc::spmv_structure(sym->S, rp, ci, sp);
+    } catch (const std::bad_alloc&) {
+        return SC_ERR_NOMEM;
+    }
+}
+
+// the handle, nrhs and up to three n x nrhs arrays with their leading dimensions
+struct PanelArg {
+    const void* p;
+    int64_t ld;
+    const char* name;
+};
+static int64_t panel_args(sc_numeric* num, int32_t nrhs, std::initializer_list<PanelArg> arrays, const char* who) {
+    std::string bad;
+    if (!num || !num->N)
+        bad = "null handle";
+    else if (nrhs < 0)
+        bad = "nrhs < 0";
+    else
+        for (const PanelArg& a : arrays) {
+            if (a.ld < num->N->S->n)
+                bad = std::string("leading dimension of ") + a.name + " below n";
+            else if (nrhs > 0 && num->N->S->n > 0 && !a.p)
+                bad = std::string("null ") + a.name;
+            if (!bad.empty()) break;
+        }
+    if (bad.empty()) return SC_OK;
+    g_last_error = std::string(who) + ": " + bad;
+    return SC_ERR_ARG;
+}
+
+static int64_t spmv_multi(sc_numeric* num, int32_t nrhs, const double* Ax, const double* X, int64_t ldx, double* Y,
+                          int64_t ldy, bool host, const char* who) {
+    int64_t rc = panel_args(num, nrhs, {{X, ldx, "X"}, {Y, ldy, "Y"}}, who);
+    if (rc != SC_OK) return rc;
+    if (nrhs > 0 && num->N->S->n > 0 && (const double*)Y == X) {
+        g_last_error = std::string(who) + ": Y aliases X";
+        return SC_ERR_ARG;
+    }
+    try {
+        rc = sc::numeric_spmv(*num->N, nrhs, Ax, X, ldx, Y, ldy, host, who);
+    } catch (const std::bad_alloc&) {
+        return SC_ERR_NOMEM;
+    }
+    if (rc < 0) g_last_error = num->N->err;
+    return rc;
+}
+
+int64_t sc_spmv_host_multi(sc_numeric* num, int32_t nrhs, const double* Ax, const double* X, int64_t ldx, double* Y,
+                           int64_t ldy) {
+    return spmv_multi(num, nrhs, Ax, X, ldx, Y, ldy, true, "sc_spmv_host_multi");
+}
+int64_t sc_spmv_device_multi(sc_numeric* num, int32_t nrhs, const double* d_Ax, const double* d_X, int64_t ldx,
+                             double* d_Y, int64_t ldy) {
+    return spmv_multi(num, nrhs, d_Ax, d_X, ldx, d_Y, ldy, false, "sc_spmv_device_multi");
+}
+
+static int64_t residual_mode_arg(int32_t residual, const char* who) {
+    if (residual == SC_RESIDUAL_FP64 || residual == SC_RESIDUAL_DD) return SC_OK;
+    g_last_error = std::string(who) + ": residual is neither SC_RESIDUAL_FP64 nor SC_RESIDUAL_DD";
+    return SC_ERR_ARG;
+}
+
+static int64_t residual_multi(sc_numeric* num, int32_t residual, int32_t nrhs, const double* Ax, const double* B,
+                              int64_t ldb, const double* X, int64_t ldx, double* R, int64_t ldr, double* berr_norm,
+                              double* berr_comp, bool host, const char* who) {
+    int64_t rc = panel_args(num, nrhs, {{B, ldb, "B"}, {X, ldx, "X"}, {R, ldr, "R"}}, who);
+    if (rc == SC_OK) rc = residual_mode_arg(residual, who);
+    if (rc != SC_OK) return rc;
+    if (nrhs > 0 && num->N->S->n > 0 && ((const double*)R == X || (const double*)R == B)) {
+        g_last_error = std::string(who) + ": R aliases B or X";
+        return SC_ERR_ARG;
+    }
+    try {
+        rc = sc::numeric_residual(*num->N, residual, nrhs, Ax, B, ldb, X, ldx, R, ldr, berr_norm, berr_comp, host, who);
+    } catch (const std::bad_alloc&) {
+        return SC_ERR_NOMEM;
+    }
+    if (rc < 0) g_last_error = num->N->err;
+    return rc;
+}
+
+int64_t sc_residual_host_multi(sc_numeric* num, int32_t residual, int32_t nrhs, const double* Ax, const double* B,
+                               int64_t ldb, const double* X, int64_t ldx, double* R, int64_t ldr, double* berr_norm,
+                               double* berr_comp) {
+    return residual_multi(num, residual, nrhs, Ax, B, ldb, X, ldx, R, ldr, berr_norm, berr_comp, true,
+                          "sc_residual_host_multi");
+}
+int64_t sc_residual_device_multi(sc_numeric* num, int32_t residual, int32_t nrhs, const double* d_Ax,
+                                 const double* d_B, int64_t ldb, const double* d_X, int64_t ldx, double* d_R,
+                                 int64_t ldr, double* berr_norm, double* berr_comp) {
+    return residual_multi(num, residual, nrhs, d_Ax, d_B, ldb, d_X, ldx, d_R, ldr, berr_norm, berr_comp, false,
+                          "sc_residual_device_multi");
+}
+
+static int64_t refine_multi(sc_numeric* num, const sc_refine_options* opt, int32_t nrhs, const double* Ax,
+                            const double* B, int64_t ldb, double* X, int64_t ldx, sc_refine_info* info, bool host,
+                            const char* who) {
+    int64_t rc = panel_args(num, nrhs, {{B, ldb, "B"}, {X, ldx, "X"}}, who);
+    if (rc != SC_OK) return rc;
+    sc_refine_options o;
+    sc_default_refine_options(&o);
+    const char* bad = nullptr;
+    if (opt) {
+        if (opt->struct_size != (int32_t)sizeof(sc_refine_options))
+            bad = "sc_refine_options.struct_size does not match this library's sizeof(sc_refine_options): initialise "
+                  "the options with sc_default_refine_options()";
+        else
+            o = *opt;
+    }
+    if (!bad && o.max_iter < 0) bad = "max_iter < 0";
+    if (!bad && !(o.rho_max > 0.0 && o.rho_max < 1.0)) bad = "rho_max outside (0, 1)";
+    if (!bad && nrhs > 0 && num->N->S->n > 0 && (const double*)X == B)
+        bad = "X aliases B (refinement needs B after X exists)";
+    if (bad) {
+        g_last_error = std::string(who) + ": " + bad;
+        return SC_ERR_ARG;
+    }
+    rc = residual_mode_arg(o.residual, who);
+    if (rc != SC_OK) return rc;
+    try {
+        rc = sc::numeric_solve_refine(*num->N, o, nrhs, Ax, B, ldb, X, ldx, info, host, who);
+    } catch (const std::bad_alloc&) {
+        return SC_ERR_NOMEM;
+    }
+    if (rc < 0) g_last_error = num->N->err;
+    return rc;
+}
+
+int64_t sc_solve_refine_host_multi(sc_numeric* num, const sc_refine_options* opt, int32_t nrhs, const double* Ax,
+                                   const double* B, int64_t ldb, double* X, int64_t ldx, sc_refine_info* info) {
+    return refine_multi(num, opt, nrhs, Ax, B, ldb, X, ldx, info, true, "sc_solve_refine_host_multi");
+}
+int64_t sc_solve_refine_device_multi(sc_numeric* num, const sc_refine_options* opt, int32_t nrhs, const double* d_Ax,
+                                     const double* d_B, int64_t ldb, double* d_X, int64_t ldx, sc_refine_info* info) {
+    return refine_multi(num, opt, nrhs, d_Ax, d_B, ldb, d_X, ldx, info, false, "sc_solve_refine_device_multi");
+}
+
+int64_t sc_debug_spmv(int32_t mode, int32_t n, const int64_t* rp, const int32_t* ci, const int64_t* sp, int64_t nval,
+                      const double* d_Ax, int32_t nrhs, const double* d_X, int64_t ldx, const double* d_B, int64_t ldb,
+                      double* d_R, int64_t ldr, double* d_W, int64_t ldw, double* d_norms) {
+    try {
+        return sc::debug_spmv(mode, n, rp, ci, sp, nval, d_Ax, nrhs, d_X, ldx, d_B, ldb, d_R, ldr, d_W, ldw, d_norms,
+                              g_last_error);
+    } catch (const std::bad_alloc&) {
+        return SC_ERR_NOMEM;
+    }
 }
 
 // ---- reference-API helpers ----

@@ -3774,4 +3774,275 @@ hipError_t launch_schur_scatter(const int32_t* idx, int ns, int nr, const double
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------
+// Products with A itself and residuals (refine.cpp).  A is the gather
+// structure of spmv.cpp: the full symmetric matrix by rows, values read through sp from the
+// caller's Ax.  Sixteen lanes share a task (one broadcast load of ci, sp and the value per
+// entry) and each owns a right-hand side; X sits in the panel family's 16-wide row-major
+// form, so one gathered row of X is one 128-byte line.  A task is a row or, for a row longer
+// than SPMV_CH, one chunk of it, whose partial the combine pass adds in chunk order.  Every
+// sum runs in one fixed order and the norms are maxima: no atomics, bitwise repeatable.
+//
+// The compensated mode is Dot2 (Ogita, Rump, Oishi 2005): every product is split exactly by
+// an fma (TwoProd), every addition by TwoSum, the error terms are collected in a second
+// double and added once at the end.  Device code is compiled with contraction on, which
+// would fuse the a * x of TwoProd into the following subtraction and make its error term
+// zero; the transforms therefore switch it off for their own statements.
+__device__ __forceinline__ void spmv_two_sum(double a, double b, double& s, double& err) {
+#pragma clang fp contract(off)
+    s = a + b;
+    const double bb = s - a;
+    err = (a - (s - bb)) + (b - bb);
+}
+
+// (s, e) -= a x, exactly but for the rounding of e
+__device__ __forceinline__ void spmv_dd_sub_prod(double a, double x, double& s, double& e) {
+#pragma clang fp contract(off)
+    const double h = a * x;
+    const double pe = __builtin_fma(a, x, -h);  // a x = h + pe
+    double q;
+    spmv_two_sum(s, -h, s, q);
+    e += q - pe;
+}
+
+// maximum that keeps a NaN once it has seen one, whatever the order
+__device__ __forceinline__ double spmv_nmax(double a, double b) { return (b > a || b != b) ? b : a; }
+
+struct SpmvAcc {
+    double s, e, w, a;
+};
+
+// the finished row: the result rounded once, its share of the column norms
+template <int MODE>
+__device__ __forceinline__ void spmv_finish(const SpmvAcc& A, double b, int row, int c, int nrhs,
+                                            const double* __restrict__ xt, double* __restrict__ R, int64_t ldr,
+                                            double* __restrict__ W, int64_t ldw, double (&nq)[SPMV_NQ]) {
+    const double r = MODE == SPMV_RES_DD ? A.s + A.e : A.s;
+    if (c < nrhs) {
+        R[row + (int64_t)c * ldr] = r;
+        if (MODE != SPMV_MUL && W) W[row + (int64_t)c * ldw] = A.w;
+    }
+    if (MODE != SPMV_MUL) {
+        const double ar = fabs(r);
+        // |r| / w with 0 / 0 = 0 and nonzero / 0 = +inf
+        const double om = A.w == 0.0 ? (ar == 0.0 ? 0.0 : __builtin_inf()) : ar / A.w;
+        nq[0] = spmv_nmax(nq[0], ar);
+        nq[1] = spmv_nmax(nq[1], fabs(xt[(int64_t)SOLVE_RHS * row + c]));
+        nq[2] = spmv_nmax(nq[2], fabs(b));
+        nq[3] = spmv_nmax(nq[3], om);
+        if (c < nrhs) nq[4] = spmv_nmax(nq[4], A.a);  // a padding column reports zeros throughout
+    }
+}
+
+// the workgroup's maxima (16 task groups x 16 columns) to its slot of the norm partials
+__device__ __forceinline__ void spmv_block_norms(const double (&nq)[SPMV_NQ], double* __restrict__ slot) {
+    __shared__ double red[SPMV_NQ][16][SOLVE_RHS];
+    const int tid = threadIdx.x, c = tid & 15, g = tid >> 4;
+#pragma unroll
+    for (int q = 0; q < SPMV_NQ; ++q) red[q][g][c] = nq[q];
+    __syncthreads();
+    if (tid < SPMV_NQ * SOLVE_RHS) {
+        const int q = tid >> 4;
+        double v = red[q][0][c];
+        for (int k = 1; k < 16; ++k) v = spmv_nmax(v, red[q][k][c]);
+        slot[tid] = v;
+    }
+}
+
+template <int MODE>
+__global__ __launch_bounds__(256) void spmv_sym_panel_kernel(SpmvPlan P, const double* __restrict__ Ax,
+                                                             const double* __restrict__ xt, int nrhs,
+                                                             const double* __restrict__ B, int64_t ldb,
+                                                             double* __restrict__ R, int64_t ldr,
+                                                             double* __restrict__ W, int64_t ldw) {
+    const int tid = threadIdx.x, c = tid & 15, g = tid >> 4;
+    double nq[SPMV_NQ] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    const int64_t t0 = (int64_t)blockIdx.x * SPMV_TPB;
+    for (int it = 0; it < SPMV_TPB / 16; ++it) {
+        const int64_t t = t0 + 16 * it + g;
+        if (t >= P.ntask) break;
+        const SpmvTask T = P.task[t];
+        const int64_t rb = P.rp[T.row], re = P.rp[T.row + 1];
+        const int64_t e1 = T.e0 + SPMV_CH < re ? T.e0 + SPMV_CH : re;
+        // b enters as the first term of the row's first task
+        double b = 0.0;
+        if (MODE != SPMV_MUL && T.e0 == rb && c < nrhs) b = B[T.row + (int64_t)c * ldb];
+        SpmvAcc A = {b, 0.0, fabs(b), 0.0};
+#pragma unroll 4
+        for (int64_t e = T.e0; e < e1; ++e) {
+            const double a = Ax[P.sp[e]];
+            const double x = xt[(int64_t)SOLVE_RHS * P.ci[e] + c];
+            if (MODE == SPMV_MUL) {
+                A.s = fma(a, x, A.s);
+            } else {
+                if (MODE == SPMV_RES_FP64)
+                    A.s = fma(-a, x, A.s);
+                else
+                    spmv_dd_sub_prod(a, x, A.s, A.e);
+                A.w = fma(fabs(a), fabs(x), A.w);
+                A.a += fabs(a);
+            }
+        }
+        if (T.slot < 0) {
+            spmv_finish<MODE>(A, b, T.row, c, nrhs, xt, R, ldr, W, ldw, nq);
+        } else {
+            double* p = P.part + (int64_t)T.slot * (SPMV_PQ * SOLVE_RHS) + c;
+            p[0] = A.s;
+            p[SOLVE_RHS] = A.e;
+            p[2 * SOLVE_RHS] = A.w;
+            p[3 * SOLVE_RHS] = A.a;
+        }
+    }
+    if (MODE != SPMV_MUL) spmv_block_norms(nq, P.nrm + (int64_t)blockIdx.x * (SPMV_NQ * SOLVE_RHS));
+}
+
+// Long rows: the chunk partials in chunk order (pairs by TwoSum in the compensated mode).
+// slot0: the first norm slot of this pass, after the row pass's.
+template <int MODE>
+__global__ __launch_bounds__(256) void spmv_combine_kernel(SpmvPlan P, const double* __restrict__ xt, int nrhs,
+                                                           const double* __restrict__ B, int64_t ldb,
+                                                           double* __restrict__ R, int64_t ldr,
+                                                           double* __restrict__ W, int64_t ldw, int64_t slot0) {
+    const int tid = threadIdx.x, c = tid & 15, g = tid >> 4;
+    double nq[SPMV_NQ] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    const int l = blockIdx.x * 16 + g;
+    if (l < P.nlong) {
+        const SpmvLong Lr = P.lrow[l];
+        const int64_t len = P.rp[Lr.row + 1] - P.rp[Lr.row];
+        const int nch = (int)((len + SPMV_CH - 1) / SPMV_CH);
+        const double* p = P.part + (int64_t)Lr.slot0 * (SPMV_PQ * SOLVE_RHS) + c;
+        SpmvAcc A = {p[0], p[SOLVE_RHS], p[2 * SOLVE_RHS], p[3 * SOLVE_RHS]};
+        for (int j = 1; j < nch; ++j) {
+            p += SPMV_PQ * SOLVE_RHS;
+            if (MODE == SPMV_RES_DD) {
+                double q;
+                spmv_two_sum(A.s, p[0], A.s, q);
+                A.e += q + p[SOLVE_RHS];
+            } else {
+                A.s += p[0];
+            }
+            A.w += p[2 * SOLVE_RHS];
+            A.a += p[3 * SOLVE_RHS];
+        }
+        const double b = (MODE != SPMV_MUL && c < nrhs) ? B[Lr.row + (int64_t)c * ldb] : 0.0;
+        spmv_finish<MODE>(A, b, Lr.row, c, nrhs, xt, R, ldr, W, ldw, nq);
+    }
+    if (MODE != SPMV_MUL) spmv_block_norms(nq, P.nrm + (slot0 + blockIdx.x) * (SPMV_NQ * SOLVE_RHS));
+}
+
+// out[SOLVE_RHS q + c] = max over the slots of part[(slot nq + q) SOLVE_RHS + c]
+__global__ __launch_bounds__(256) void spmv_norm_final_kernel(const double* __restrict__ part, int64_t nslots, int nq,
+                                                              double* __restrict__ out) {
+    __shared__ double red[16][SOLVE_RHS];
+    const int tid = threadIdx.x, c = tid & 15, g = tid >> 4;
+    for (int q = 0; q < nq; ++q) {
+        double v = 0.0;
+        for (int64_t s = g; s < nslots; s += 16) v = spmv_nmax(v, part[(s * nq + q) * SOLVE_RHS + c]);
+        red[g][c] = v;
+        __syncthreads();
+        if (g == 0) {
+            for (int k = 1; k < 16; ++k) v = spmv_nmax(v, red[k][c]);
+            out[SOLVE_RHS * q + c] = v;
+        }
+        __syncthreads();
+    }
+}
+
+// 64 rows per workgroup through LDS, so both sides move in runs; columns >= nrhs are zero
+__global__ __launch_bounds__(256) void spmv_transpose_kernel(double* __restrict__ xt, const double* __restrict__ X,
+                                                             int64_t ldx, int64_t n, int nrhs) {
+    __shared__ double tile[64][SOLVE_RHS + 1];
+    const int tid = threadIdx.x, il = tid & 63, jq = tid >> 6;
+    const int64_t i0 = (int64_t)blockIdx.x * 64, i = i0 + il;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int c = jq + 4 * q;
+        tile[il][c] = (i < n && c < nrhs) ? X[i + (int64_t)c * ldx] : 0.0;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int e = tid + 256 * q;
+        if (i0 + (e >> 4) < n) xt[i0 * SOLVE_RHS + e] = tile[e >> 4][e & 15];
+    }
+}
+
+// column c = blockIdx.y: max |D(i, c)| over the rows of workgroup blockIdx.x's stride
+__global__ __launch_bounds__(256) void refine_dnorm_kernel(const double* __restrict__ D, int64_t ldd, int64_t n,
+                                                           int nrhs, double* __restrict__ part) {
+    __shared__ double red[256];
+    const int c = blockIdx.y;
+    double v = 0.0;
+    if (c < nrhs)
+        for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)REFINE_NG * 256)
+            v = spmv_nmax(v, fabs(D[i + (int64_t)c * ldd]));
+    red[threadIdx.x] = v;
+    __syncthreads();
+    for (int h = 128; h > 0; h >>= 1) {
+        if ((int)threadIdx.x < h) red[threadIdx.x] = spmv_nmax(red[threadIdx.x], red[threadIdx.x + h]);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) part[blockIdx.x * SOLVE_RHS + c] = red[0];
+}
+
+__global__ __launch_bounds__(256) void refine_add_kernel(double* __restrict__ X, int64_t ldx,
+                                                         const double* __restrict__ D, int64_t ldd, int64_t n,
+                                                         uint32_t mask) {
+    const int c = blockIdx.y;
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n && ((mask >> c) & 1u)) X[i + (int64_t)c * ldx] += D[i + (int64_t)c * ldd];
+}
+
+hipError_t launch_spmv_transpose(double* xt, const double* X, int64_t ldx, int64_t n, int nrhs, hipStream_t st) {
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(spmv_transpose_kernel, dim3((unsigned)((n + 63) / 64)), dim3(256), 0, st, xt, X, ldx, n, nrhs);
+    return hipGetLastError();
+}
+
+template <int MODE>
+static void spmv_launch_mode(const SpmvPlan& P, const double* Ax, const double* xt, int nrhs, const double* B,
+                             int64_t ldb, double* R, int64_t ldr, double* W, int64_t ldw, hipStream_t st) {
+    const int64_t g1 = spmv_row_groups(P.ntask), g2 = spmv_long_groups(P.nlong);
+    hipLaunchKernelGGL(spmv_sym_panel_kernel<MODE>, dim3((unsigned)g1), dim3(256), 0, st, P, Ax, xt, nrhs, B, ldb, R,
+                       ldr, W, ldw);
+    if (g2 > 0)
+        hipLaunchKernelGGL(spmv_combine_kernel<MODE>, dim3((unsigned)g2), dim3(256), 0, st, P, xt, nrhs, B, ldb, R, ldr,
+                           W, ldw, g1);
+}
+
+hipError_t launch_spmv_sym_panel(const SpmvPlan& P, int mode, const double* Ax, const double* xt, int nrhs,
+                                 const double* B, int64_t ldb, double* R, int64_t ldr, double* W, int64_t ldw,
+                                 double* out, hipStream_t st) {
+    if (mode < SPMV_MUL || mode > SPMV_RES_DD || nrhs < 0 || nrhs > SOLVE_RHS) return hipErrorInvalidValue;
+    if (P.n <= 0 || P.ntask <= 0) {
+        if (out && mode != SPMV_MUL) return hipMemsetAsync(out, 0, sizeof(double) * SPMV_NQ * SOLVE_RHS, st);
+        return hipSuccess;
+    }
+    if (mode == SPMV_MUL)
+        spmv_launch_mode<SPMV_MUL>(P, Ax, xt, nrhs, B, ldb, R, ldr, W, ldw, st);
+    else if (mode == SPMV_RES_FP64)
+        spmv_launch_mode<SPMV_RES_FP64>(P, Ax, xt, nrhs, B, ldb, R, ldr, W, ldw, st);
+    else
+        spmv_launch_mode<SPMV_RES_DD>(P, Ax, xt, nrhs, B, ldb, R, ldr, W, ldw, st);
+    if (out && mode != SPMV_MUL)
+        hipLaunchKernelGGL(spmv_norm_final_kernel, dim3(1), dim3(256), 0, st, P.nrm,
+                           spmv_row_groups(P.ntask) + spmv_long_groups(P.nlong), SPMV_NQ, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_refine_dnorm(const double* D, int64_t ldd, int64_t n, int nrhs, double* part, double* out,
+                               hipStream_t st) {
+    hipLaunchKernelGGL(refine_dnorm_kernel, dim3(REFINE_NG, SOLVE_RHS), dim3(256), 0, st, D, ldd, n, nrhs, part);
+    hipLaunchKernelGGL(spmv_norm_final_kernel, dim3(1), dim3(256), 0, st, part, (int64_t)REFINE_NG, 1, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_refine_add(double* X, int64_t ldx, const double* D, int64_t ldd, int64_t n, int nrhs, uint32_t mask,
+                             hipStream_t st) {
+    if (n <= 0 || nrhs <= 0 || mask == 0) return hipSuccess;
+    hipLaunchKernelGGL(refine_add_kernel, dim3((unsigned)((n + 255) / 256), nrhs), dim3(256), 0, st, X, ldx, D, ldd, n,
+                       mask);
+    return hipGetLastError();
+}
+
 }  // namespace sc

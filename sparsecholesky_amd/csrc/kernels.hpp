@@ -305,6 +305,58 @@ hipError_t launch_schur_mul_t(const double* D, int ns, int nr, const double* X, 
 hipError_t launch_schur_scatter(const int32_t* idx, int ns, int nr, const double* XS, int64_t ldxs, double* X,
                                 int64_t ldx, hipStream_t st);
 
+// ---- products with A itself and residuals (refine.cpp) ----
+// The full symmetric A by rows, in A's own numbering (spmv.cpp): row i holds entries
+// [rp[i], rp[i + 1]) with ascending columns ci and sp, the index of the value in the
+// caller's Ax.  Rows are cut into tasks of at most SPMV_CH entries; a row of several tasks
+// leaves one partial per task (slot >= 0, consecutive in chunk order) and is finished by
+// the combine pass over the long-row list.
+constexpr int SPMV_CH = 256;    // entries per task: a dense row must not run as one serial loop
+constexpr int SPMV_TPB = 256;   // tasks per workgroup of the row pass (16 at a time, one per 16 lanes)
+constexpr int SPMV_NQ = 5;      // norms per column: max |r|, max |x|, max |b|, max |r| / w, max row sum of |A|
+constexpr int SPMV_PQ = 4;      // doubles per partial and column: sum, error term, w, row sum of |A|
+enum SpmvMode : int32_t { SPMV_MUL = 0, SPMV_RES_FP64 = 1, SPMV_RES_DD = 2 };
+struct SpmvTask {
+    int64_t e0;      // first entry
+    int32_t row;
+    int32_t slot;    // partial slot, or -1: the task is the whole row
+};
+struct SpmvLong {
+    int32_t row;
+    int32_t slot0;   // first partial slot; the row has ceil(len / SPMV_CH) of them
+};
+struct SpmvPlan {
+    const int64_t* rp;
+    const int32_t* ci;
+    const int64_t* sp;
+    const SpmvTask* task;
+    const SpmvLong* lrow;
+    int64_t ntask;
+    int32_t n, nlong;
+    double* part;    // SPMV_PQ x SOLVE_RHS doubles per partial slot
+    double* nrm;     // SPMV_NQ x SOLVE_RHS doubles per workgroup of the two passes
+};
+inline int64_t spmv_row_groups(int64_t ntask) { return (ntask + SPMV_TPB - 1) / SPMV_TPB; }
+inline int64_t spmv_long_groups(int64_t nlong) { return (nlong + 15) / 16; }
+// xt[SOLVE_RHS i + c] = X(i, c) for c < nrhs, else 0 (X: n x nrhs column-major, ld = ldx)
+hipError_t launch_spmv_transpose(double* xt, const double* X, int64_t ldx, int64_t n, int nrhs, hipStream_t st);
+// One pass over A for a panel of nrhs <= SOLVE_RHS columns, X in the 16-wide row-major form
+// xt.  SPMV_MUL: R = A X (B, W, out unused).  SPMV_RES_*: R = B - A X, accumulated in fp64 or
+// as a compensated dot product (Dot2) rounded once, with w = |B| + |A| |X| in plain fp64; W
+// (may be null) receives w; out (may be null; SPMV_NQ x SOLVE_RHS, value q of column c at
+// SOLVE_RHS q + c) the column norms, reduced as maxima in a fixed order: no atomics.  B, R
+// and W are column-major; nothing outside their n x nrhs windows is read or written.
+hipError_t launch_spmv_sym_panel(const SpmvPlan& P, int mode, const double* Ax, const double* xt, int nrhs,
+                                 const double* B, int64_t ldb, double* R, int64_t ldr, double* W, int64_t ldw,
+                                 double* out, hipStream_t st);
+// out[c] = max_i |D(i, c)| for c < nrhs (part: SOLVE_RHS x REFINE_NG doubles), 0 for the rest
+constexpr int REFINE_NG = 64;
+hipError_t launch_refine_dnorm(const double* D, int64_t ldd, int64_t n, int nrhs, double* part, double* out,
+                               hipStream_t st);
+// X(i, c) += D(i, c) for the columns c whose bit is set in mask
+hipError_t launch_refine_add(double* X, int64_t ldx, const double* D, int64_t ldd, int64_t n, int nrhs, uint32_t mask,
+                             hipStream_t st);
+
 // Small fronts (m <= maxm <= 128): one workgroup per front, factored in registers
 // (4 x 4 tiles per thread); seq: one workgroup runs the fronts in order (a whole
 // small tree in postorder, CBs through HBM).

@@ -396,6 +396,15 @@ struct Numeric {
     int64_t sch_gen = -1;              // factor_gen the gathered D belongs to
     double* d_schW = nullptr;
 
+    // products with A and iterative refinement (refine.cpp; single-device handles): A as a
+    // gather structure with its task lists and partial slots, the transposed X panel, the
+    // R / D panel (n x SOLVE_RHS, ld = n) and the norm scratch, allocated at the first use, kept
+    bool spmv_ready = false;
+    SpmvPlan SPMV {};
+    double* d_rfxt = nullptr;
+    double* d_rfR = nullptr;
+    double* d_rfnorm = nullptr;        // SPMV_NQ + 1 rows of SOLVE_RHS norms, then the increment norm's partials
+
     std::string err;
 };
 
@@ -499,6 +508,28 @@ int64_t numeric_schur_condense(Numeric& N, int32_t nrhs, const double* B, int64_
                                bool host);
 int64_t numeric_schur_expand(Numeric& N, int32_t nrhs, const double* B, int64_t ldb, const double* XS, int64_t ldxs,
                              double* X, int64_t ldx, bool host);
+// Products with A, residuals and iterative refinement (refine.cpp),
+// in panels of SOLVE_RHS columns; all arrays column-major in A's own order, device or host
+// memory by `host` (the host forms stage their arrays for the length of the call).  Ax: the
+// values in the order of the analysed pattern, or null for the copy sc_factor made (SC_ERR_ARG
+// when the last factorization was not an sc_factor).  Synchronous on the handle's stream.
+// The product and the residual never look at the factor.  mode: SC_RESIDUAL_*.
+int64_t numeric_spmv(Numeric& N, int32_t nrhs, const double* Ax, const double* X, int64_t ldx, double* Y, int64_t ldy,
+                     bool host, const char* who);
+int64_t numeric_residual(Numeric& N, int32_t mode, int32_t nrhs, const double* Ax, const double* B, int64_t ldb,
+                         const double* X, int64_t ldx, double* R, int64_t ldr, double* berr_norm, double* berr_comp,
+                         bool host, const char* who);
+// X = A^-1 B by the panel solve plus refinement steps against Ax; status rules of the solves,
+// multi-rank and emulated handles SC_ERR_NOTIMPL.  opt: validated by the caller.
+int64_t numeric_solve_refine(Numeric& N, const sc_refine_options& opt, int32_t nrhs, const double* Ax, const double* B,
+                             int64_t ldb, double* X, int64_t ldx, sc_refine_info* info, bool host, const char* who);
+// The kernels alone on a caller's structure (host arrays, validated: rp ascending from 0, ci
+// in [0, n), sp in [0, nval)) and values and panels (device pointers), synchronous: mode
+// SpmvMode; X, B, R, W column-major n x nrhs (nrhs <= SOLVE_RHS); W and norms (SPMV_NQ x
+// SOLVE_RHS, device) may be null.
+int64_t debug_spmv(int32_t mode, int32_t n, const int64_t* rp, const int32_t* ci, const int64_t* sp, int64_t nval,
+                   const double* d_Ax, int32_t nrhs, const double* d_X, int64_t ldx, const double* d_B, int64_t ldb,
+                   double* d_R, int64_t ldr, double* d_W, int64_t ldw, double* d_norms, std::string& err);
 // The product kernel alone on caller data (device), synchronous.
 int64_t debug_schur_llt(const double* dD, int32_t ns, int64_t ldd, double* dS, int64_t lds);
 // The two kernels of one block step on block k0 of a caller's m x w panel and m x UPD_W

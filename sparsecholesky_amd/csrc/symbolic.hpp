@@ -119,6 +119,11 @@ i64 schur_order(i64 n, const i64* Ap, const i32* Ai, i32 ordering, i32 ns, const
 void permute_upper(i64 n, const i64* Ap, const i32* Ai, const i32* perm, std::vector<i64>& Bp,
                    std::vector<i32>& Bi, std::vector<i64>& src);
 
+// The full symmetric A by rows in A's own numbering (spmv.cpp): rp[n + 1], and when ci and
+// sp are given the ascending columns and the value indices into the caller's array.  Returns
+// the entry count.
+i64 spmv_structure(const Symbolic& S, i64* rp, i32* ci, i64* sp);
+
 // Reference-layout pattern of L (schol().p()/i()), natural numbering.
 void pattern_L(const Symbolic& S, i64* Lp, i32* Li);
 
