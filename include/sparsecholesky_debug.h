@@ -49,6 +49,34 @@ int64_t sc_debug_panel(double* dF, int32_t m, int32_t w, int32_t k0, int32_t mod
  * downdate (nothing of the block is then written). */
 int64_t sc_debug_updown_block(double* dF, int32_t m, int32_t w, int32_t k0, double* dW, int32_t sign,
                               int32_t* info);
+/* One step of the solve family on block k0 (a multiple of 128, nb = min(128, w - k0) columns)
+ * of a caller's m x w front panel (device, column-major, ld = m, 1 <= w <= m < 2^20) through
+ * a one-front plan whose row list is the identity, with the step's tasks cut as a solve cuts
+ * them.  width 1: the single-vector kernels, vectors of doubles; width 16: the panel kernels,
+ * vectors of 16-wide rows (entry (row, j) at 16 row + j).  dC: m rows (c over the front's
+ * rows), dY: w rows (op 4: m rows), dU: m - w rows (may be NULL when m == w).
+ *   op 0: the inverses of the block's one or two 64 x 64 diagonal blocks and, for nb > 64, the
+ *         off-diagonal quadrant, into the block's strict upper triangle (vectors unused);
+ *   op 1: the forward step: y_blk = X c_blk to dY, L(r, blk) y_blk subtracted from dC (rows r
+ *         < w) or dU (row r at r - w) for the rows r below the block;
+ *   op 2: the backward step: c_blk = X^T (c_blk - L(R, blk)^T c_R), R the rows below;
+ *   op 3: the L Z step: L11 z_blk added to c_blk, L(r, blk) z_blk to dC / dU below; Z in dY;
+ *   op 4: the L^T Z step: c_blk = L11^T z_blk + L(R, blk)^T z_R; Z in dY over all m rows.
+ * Ops 1 and 2 need the inverses of an op 0 call in dF; ops 3 and 4 are width 16 only.  A null
+ * pointer, k0 >= w, k0 % 128 != 0, another width or op, or a product with width 1 returns
+ * SC_ERR_ARG before any device call.  Synchronous. */
+int64_t sc_debug_solve_step(double* dF, int32_t m, int32_t w, int32_t k0, int32_t op, int32_t width, double* dC,
+                            double* dY, double* dU);
+/* The forward gather of the solves on one parent front of w >= 1 pivots and mb >= 0
+ * contribution rows (row list the identity) with nchild children taken in the order given:
+ * child q holds rel_ptr[q + 1] - rel_ptr[q] entries (width 16: 16-wide rows) of u,
+ * consecutive in dUc, and entry i goes to front row t = relind[i]: added to dC[t] for t < w,
+ * to dU[t - w] otherwise.  rel_ptr and relind are host arrays, validated before any device
+ * call (rel_ptr ascending from 0, relind in [0, w + mb) and injective within a child); dUc,
+ * dC (w rows) and dU (mb rows; NULL when mb == 0) device.  The gather runs on a copy of dUc
+ * and dU in one buffer of the hook's own; dC is the caller's.  Synchronous. */
+int64_t sc_debug_solve_gather(int32_t width, int32_t w, int32_t mb, int32_t nchild, const int64_t* rel_ptr,
+                              const int32_t* relind, const double* dUc, double* dC, double* dU);
 /* Best wall time (ms) of reps synchronous factorizations from device values
  * (sc_factor_device(num, d_Ax, 1): launch, run, status read-back), timed in C. */
 int64_t sc_debug_time_factor(sc_numeric* num, const double* d_Ax, int32_t reps, double* best_ms);

@@ -206,6 +206,8 @@ _SIGS = [
     ("sc_debug_panel", _I64, [_P, _I32, _I32, _I32, _I32, C.POINTER(_I32)]),
     ("sc_debug_updown_block", _I64, [_P, _I32, _I32, _I32, _P, _I32, C.POINTER(_I32)]),
     ("sc_debug_schur_llt", _I64, [_P, _I32, _I64, _P, _I64]),
+    ("sc_debug_solve_step", _I64, [_P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P]),
+    ("sc_debug_solve_gather", _I64, [_I32, _I32, _I32, _I32, _P, _P, _P, _P, _P]),
     ("sc_debug_spmv", _I64, [_I32, _I32, _P, _P, _P, _I64, _P, _I32, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _P]),
     ("sc_debug_bench", _I64, [_I32, _I32, _I32, _I32, _I32, C.POINTER(_D)]),
     ("sc_device_count", _I64, []),

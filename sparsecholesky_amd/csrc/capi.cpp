@@ -1183,6 +1183,18 @@ int64_t sc_debug_updown_block(double* dF, int32_t m, int32_t w, int32_t k0, doub
     return sc::debug_updown_block(dF, m, w, k0, dW, sign, info);
 }
 
+int64_t sc_debug_solve_step(double* dF, int32_t m, int32_t w, int32_t k0, int32_t op, int32_t width, double* dC,
+                            double* dY, double* dU) {
+    if (!dF || !dC || !dY) return SC_ERR_ARG;
+    return sc::debug_solve_step(dF, m, w, k0, op, width, dC, dY, dU);
+}
+
+int64_t sc_debug_solve_gather(int32_t width, int32_t w, int32_t mb, int32_t nchild, const int64_t* rel_ptr,
+                              const int32_t* relind, const double* dUc, double* dC, double* dU) {
+    if (!rel_ptr || !dC) return SC_ERR_ARG;
+    return sc::debug_solve_gather(width, w, mb, nchild, rel_ptr, relind, dUc, dC, dU);
+}
+
 int64_t sc_debug_bench(int32_t which, int32_t M, int32_t K, int32_t reps, int32_t arg, double* tflops) {
     if (!tflops || M <= 0 || K <= 0 || reps <= 0) return SC_ERR_ARG;
     return sc::debug_bench(which, M, K, reps, arg, tflops);

@@ -1,6 +1,7 @@
 // Debug and microbenchmark hooks (sc_debug_syrk, sc_debug_syrk_ex, sc_debug_panel,
-// sc_debug_updown_block, sc_debug_bench): the SYRK, panel and update / downdate kernels on
-// caller data, kernel ceilings on synthetic operands.
+// sc_debug_updown_block, sc_debug_solve_step, sc_debug_solve_gather, sc_debug_bench): the
+// SYRK, panel, update / downdate and solve / factor-product kernels on caller data, kernel
+// ceilings on synthetic operands.
 #include "numeric_impl.hpp"
 
 namespace sc {
@@ -181,6 +182,143 @@ int64_t debug_updown_block(double* dF, int m, int w, int k0, double* dW, int sig
     for (void* p : {d_s, d_m, d_o, d_rp, d_r, d_t, d_i})
         if (p) (void)hipFree(p);
     return rc;
+}
+
+namespace {
+
+// Device copies of small host arrays, freed together.
+struct DevArrays {
+    std::vector<void*> ptrs;
+    int64_t rc = SC_OK;
+    void* raw(size_t bytes) {
+        void* d = nullptr;
+        if (rc != SC_OK) return nullptr;
+        if (hipMalloc(&d, std::max<size_t>(bytes, 8)) != hipSuccess) {
+            rc = SC_ERR_DEVMEM;
+            return nullptr;
+        }
+        ptrs.push_back(d);
+        return d;
+    }
+    template <class T>
+    const T* put(const std::vector<T>& h) {
+        void* d = raw(h.size() * sizeof(T));
+        if (d && !h.empty() && hipMemcpy(d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess)
+            rc = SC_ERR_HIP;
+        return (const T*)d;
+    }
+    ~DevArrays() {
+        for (void* p : ptrs) (void)hipFree(p);
+    }
+};
+
+}  // namespace
+
+int64_t debug_solve_step(double* dF, int m, int w, int k0, int op, int width, double* dC, double* dY, double* dU) {
+    if (!dF || !dC || !dY || m < 1 || m >= (1 << 20) || w < 1 || w > m || (!dU && m > w) || k0 < 0 || k0 >= w ||
+        k0 % SOLVE_NB != 0 || op < 0 || op > 4 || (width != 1 && width != SOLVE_RHS) || (op >= 3 && width != SOLVE_RHS))
+        return SC_ERR_ARG;
+    // the step's tasks of the one front, as solve_build cuts them
+    SolveCut cut;
+    solve_cut_front(0, w, m, k0, 0, cut);
+    std::vector<int32_t> rows((size_t)m);
+    for (int i = 0; i < m; ++i) rows[(size_t)i] = i;
+    DevArrays A;
+    SolvePlan P {};
+    P.sn_start = A.put(std::vector<int32_t> {0, w});
+    P.sn_m = A.put(std::vector<int32_t> {m});
+    P.panel_off = A.put(std::vector<int64_t> {0});
+    P.rows_ptr = A.put(std::vector<int64_t> {0, m});
+    P.rows = A.put(rows);
+    P.u_off = A.put(std::vector<int64_t> {0});
+    P.panel_pool = dF;
+    P.c = dC;
+    P.y = dY;
+    P.u = dU;
+    P.part = (double*)A.raw(std::max<size_t>(cut.bwd.size(), 1) * SOLVE_NB * (size_t)width * sizeof(double));
+    const int2 *d_i64 = A.put(cut.inv64), *d_i128 = A.put(cut.inv128);
+    const int4 *d_diag = A.put(cut.diag), *d_bwd = A.put(cut.bwd), *d_fwd = A.put(cut.fwd);
+    if (A.rc != SC_OK) return A.rc;
+    const int nf = (int)cut.fwd.size(), ng = (int)cut.bwd.size(), nd = (int)cut.diag.size();
+    const bool one = width == 1;
+    hipError_t e = hipSuccess;
+    switch (op) {
+        case 0: e = launch_solve_inv(P, d_i64, (int)cut.inv64.size(), d_i128, (int)cut.inv128.size(), nullptr); break;
+        case 1: e = one ? launch_solve_fwd(P, d_fwd, nf, nullptr) : launch_solve_fwd_multi(P, d_fwd, nf, nullptr); break;
+        case 2:
+            e = one ? launch_solve_gemv(P, d_bwd, ng, nullptr) : launch_solve_gemv_multi(P, d_bwd, ng, nullptr);
+            if (e == hipSuccess)
+                e = one ? launch_solve_diag(P, d_diag, nd, nullptr) : launch_solve_diag_multi(P, d_diag, nd, nullptr);
+            break;
+        case 3: e = launch_mul_l_multi(P, d_fwd, nf, nullptr); break;
+        default:
+            e = launch_mul_lt_gemv_multi(P, d_bwd, ng, nullptr);
+            if (e == hipSuccess) e = launch_mul_lt_diag_multi(P, d_diag, nd, nullptr);
+    }
+    const hipError_t e2 = hipDeviceSynchronize();
+    return (e == hipSuccess && e2 == hipSuccess) ? SC_OK : SC_ERR_HIP;
+}
+
+int64_t debug_solve_gather(int width, int w, int mb, int nchild, const int64_t* rel_ptr, const int32_t* relind,
+                           const double* dUc, double* dC, double* dU) {
+    if ((width != 1 && width != SOLVE_RHS) || w < 1 || mb < 0 || (int64_t)w + mb >= (1 << 20) || nchild < 0 ||
+        nchild > (1 << 20) || !rel_ptr || !dC || (!dU && mb > 0) || rel_ptr[0] != 0)
+        return SC_ERR_ARG;
+    for (int q = 0; q < nchild; ++q)
+        if (rel_ptr[q + 1] < rel_ptr[q] || rel_ptr[q + 1] - rel_ptr[q] > w + mb) return SC_ERR_ARG;  // injective: <= w + mb
+    const int64_t tot = rel_ptr[nchild];
+    if (tot > 0 && (!relind || !dUc)) return SC_ERR_ARG;
+    {
+        std::vector<int32_t> seen((size_t)(w + mb), -1);
+        for (int q = 0; q < nchild; ++q)
+            for (int64_t i = rel_ptr[q]; i < rel_ptr[q + 1]; ++i) {
+                const int32_t t = relind[i];
+                if (t < 0 || t >= w + mb || seen[(size_t)t] == q) return SC_ERR_ARG;
+                seen[(size_t)t] = q;
+            }
+    }
+    // supernodes 0 .. nchild - 1 the children (only their u and relind are looked at), nchild
+    // the parent; u: the children's entries back to back, then the parent's mb rows
+    const int ns = nchild + 1;
+    std::vector<int32_t> sn_start((size_t)ns + 1, 0), child_ptr((size_t)ns + 1, 0), child_list((size_t)nchild);
+    std::vector<int64_t> rows_ptr((size_t)ns + 1, 0), u_off((size_t)ns), relp((size_t)ns + 1);
+    std::vector<int32_t> rows((size_t)(w + mb)), front {nchild};
+    sn_start[(size_t)ns] = w;
+    rows_ptr[(size_t)ns] = w + mb;
+    child_ptr[(size_t)ns] = nchild;
+    for (int q = 0; q < nchild; ++q) {
+        child_list[(size_t)q] = q;
+        u_off[(size_t)q] = rel_ptr[q];
+        relp[(size_t)q] = rel_ptr[q];
+    }
+    u_off[(size_t)nchild] = tot;
+    relp[(size_t)nchild] = relp[(size_t)ns] = tot;
+    for (int i = 0; i < w + mb; ++i) rows[(size_t)i] = i;
+    DevArrays A;
+    SolvePlan P {};
+    P.sn_start = A.put(sn_start);
+    P.rows_ptr = A.put(rows_ptr);
+    P.rows = A.put(rows);
+    P.u_off = A.put(u_off);
+    P.child_ptr = A.put(child_ptr);
+    P.child_list = A.put(child_list);
+    P.rel_ptr = A.put(relp);
+    P.relind = A.put(std::vector<int32_t>(relind, relind + tot));
+    const int32_t* d_front = A.put(front);
+    const size_t wide = (size_t)width * sizeof(double);
+    double* u = (double*)A.raw((size_t)(tot + mb) * wide);
+    if (A.rc != SC_OK) return A.rc;
+    P.c = dC;
+    P.u = u;
+    if (tot > 0 && hipMemcpy(u, dUc, (size_t)tot * wide, hipMemcpyDeviceToDevice) != hipSuccess) return SC_ERR_HIP;
+    if (mb > 0 && hipMemcpy(u + tot * width, dU, (size_t)mb * wide, hipMemcpyDeviceToDevice) != hipSuccess)
+        return SC_ERR_HIP;
+    hipError_t e = width == 1 ? launch_solve_fwd_gather(P, d_front, 1, nullptr)
+                              : launch_solve_fwd_gather_multi(P, d_front, 1, nullptr);
+    const hipError_t e2 = hipDeviceSynchronize();
+    if (e == hipSuccess && e2 == hipSuccess && mb > 0)
+        e = hipMemcpy(dU, u + tot * width, (size_t)mb * wide, hipMemcpyDeviceToDevice);
+    return (e == hipSuccess && e2 == hipSuccess) ? SC_OK : SC_ERR_HIP;
 }
 
 // Panel-kernel microbenchmarks on one synthetic front (m = M rows, w = 64):

@@ -535,6 +535,13 @@ int64_t debug_schur_llt(const double* dD, int32_t ns, int64_t ldd, double* dS, i
 // The two kernels of one block step on block k0 of a caller's m x w panel and m x UPD_W
 // workspace (device; dW row-major, row = front row), through a one-front plan.
 int64_t debug_updown_block(double* dF, int m, int w, int k0, double* dW, int sign, int32_t* info);
+// One 128-column step of the solve family on block k0 of a caller's m x w panel through a
+// one-front plan whose row list is the identity (op 0 inverses, 1 forward, 2 backward, 3 L Z,
+// 4 L^T Z; width 1 or SOLVE_RHS), and the forward gather of one parent front from nchild
+// children (rel_ptr, relind: host).  include/sparsecholesky_debug.h has the contracts.
+int64_t debug_solve_step(double* dF, int m, int w, int k0, int op, int width, double* dC, double* dY, double* dU);
+int64_t debug_solve_gather(int width, int w, int mb, int nchild, const int64_t* rel_ptr, const int32_t* relind,
+                           const double* dUc, double* dC, double* dU);
 // Destroys the captured solve and apply graphs (they point at one panel pool).
 void numeric_drop_solve_graphs(Numeric& N);
 int64_t debug_syrk(double* dC, int ldc, const double* dA, int lda, int M, int N, int K);

@@ -108,6 +108,15 @@ int64_t apply_prepare(Numeric& N);
 // The diagonal-block inverses of the current factorization in place (launch_solve_inv,
 // once per factorization; shared by the solves, the half solves and the selected inversion).
 int64_t solve_inverses(Numeric& N);
+// The solve task lists (launch_solve_inv's two, the diagonal kernels', the backward GEMV's,
+// the forward kernels') and how one front (s: m rows, w > k0 columns) adds its tasks of the
+// 128-column step k0 to them; goff: where the step's GEMV tasks start in bwd (a diagonal task
+// addresses its partials relative to that).  solve_build and sc_debug_solve_step cut with it.
+struct SolveCut {
+    std::vector<int2> inv64, inv128;
+    std::vector<int4> diag, bwd, fwd;
+};
+void solve_cut_front(int32_t s, int w, int m, int k0, int64_t goff, SolveCut& C);
 
 // dist.cpp
 hipError_t comm_launch(Numeric& N, const Launch& L);

@@ -92,6 +92,26 @@ int64_t numeric_export_cols(Numeric& N, int64_t j0, int64_t j1, int64_t* cp, int
     return tot;
 }
 
+// One front's tasks of the 128-column step k0 (numeric_impl.hpp): the diagonal task with its
+// ng GEMV partials, the 64-block and 128-quadrant inverse tasks, then SOLVE_ROWS rows per
+// backward GEMV / forward task from the block's end down; the forward list keeps one task
+// (r0 = -1) for a block with no rows below, and its first task is the writer of y.
+void solve_cut_front(int32_t s, int w, int m, int k0, int64_t goff, SolveCut& C) {
+    const int rb = std::min(w, k0 + SOLVE_NB);
+    const int ng = rb < m ? (m - rb + SOLVE_ROWS - 1) / SOLVE_ROWS : 0;
+    C.diag.push_back(make_int4(s, k0, (int)((int64_t)C.bwd.size() - goff), ng));
+    C.inv64.push_back(make_int2(s, k0));
+    if (w > k0 + PNB) {
+        C.inv64.push_back(make_int2(s, k0 + PNB));
+        C.inv128.push_back(make_int2(s, k0));
+    }
+    if (rb >= m) C.fwd.push_back(make_int4(s, k0, -1, 1));
+    for (int r0 = rb; r0 < m; r0 += SOLVE_ROWS) {
+        C.bwd.push_back(make_int4(s, k0, r0, 0));
+        C.fwd.push_back(make_int4(s, k0, r0, r0 == rb ? 1 : 0));
+    }
+}
+
 // ---------------- triangular solves ----------------
 // A = P^T L L^T P (P = etree postorder): c = P b; L y = c (levels up); L^T x = y
 // (levels down); x = P^T c.  Per level and 64-column step, over every supernode with
@@ -102,8 +122,9 @@ static int64_t solve_build(Numeric& N) {
     const Symbolic& S = *N.S;
     std::vector<std::vector<int32_t>> by_level((size_t)S.nlevels);
     for (int32_t s = 0; s < S.ns; ++s) by_level[S.level[s]].push_back(s);
-    std::vector<int2> inv64, inv128;
-    std::vector<int4> diag, bwd, fwd;
+    SolveCut cut;
+    std::vector<int2>&inv64 = cut.inv64, &inv128 = cut.inv128;
+    std::vector<int4>&diag = cut.diag, &bwd = cut.bwd, &fwd = cut.fwd;
     std::vector<int32_t> gather;  // per level: the fronts with children (forward gather)
     int64_t max_g = 1;            // most GEMV workgroups in one backward step
     // internal index -> index in the caller's order (postorder, then the fill-reducing
@@ -127,20 +148,7 @@ static int64_t solve_build(Numeric& N) {
             for (int32_t s : by_level[lev]) {
                 const int w = S.w(s), m = S.sn_m[s];
                 if (w <= k0) continue;
-                const int rb0 = std::min(w, k0 + SOLVE_NB);
-                const int ng = rb0 < m ? (m - rb0 + SOLVE_ROWS - 1) / SOLVE_ROWS : 0;
-                diag.push_back(make_int4(s, k0, (int)((int64_t)bwd.size() - st.goff), ng));
-                inv64.push_back(make_int2(s, k0));
-                if (w > k0 + PNB) {
-                    inv64.push_back(make_int2(s, k0 + PNB));
-                    inv128.push_back(make_int2(s, k0));
-                }
-                const int rb = std::min(w, k0 + SOLVE_NB);
-                if (rb >= m) fwd.push_back(make_int4(s, k0, -1, 1));
-                for (int r0 = rb; r0 < m; r0 += SOLVE_ROWS) {
-                    bwd.push_back(make_int4(s, k0, r0, 0));
-                    fwd.push_back(make_int4(s, k0, r0, r0 == rb ? 1 : 0));
-                }
+                solve_cut_front(s, w, m, k0, st.goff, cut);
             }
             st.dcount = (int32_t)((int64_t)diag.size() - st.doff);
             st.gcount = (int32_t)((int64_t)bwd.size() - st.goff);
