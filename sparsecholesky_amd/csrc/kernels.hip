@@ -2440,6 +2440,35 @@ __device__ __forceinline__ void diag_mfma_multi(const DiagA& A, int nb, const do
     }
 }
 
+// A 128 x 16 block of 16-wide rows between memory (p) and a workgroup of SOLVE_ROWS
+// threads, entry e = tid + SOLVE_ROWS q the thread's q-th: s is an LDS panel (entry e at
+// s[e]) or, REGS, the thread's own BLOCK_NQ values (entry e at s[q]).  block_in reads the
+// rows past nb as zeros; block_out stores (ADD: adds) the rows below nb only.
+constexpr int BLOCK_NQ = SOLVE_PANEL / SOLVE_ROWS;
+template <bool REGS = false>
+__device__ __forceinline__ void block_in(double* s, const double* p, int nb) {
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int q = 0; q < BLOCK_NQ; ++q) {
+        const int e = tid + SOLVE_ROWS * q;
+        s[REGS ? q : e] = (e >> 4) < nb ? p[e] : 0.0;
+    }
+}
+template <bool REGS = false, bool ADD = false>
+__device__ __forceinline__ void block_out(double* p, const double* s, int nb) {
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int q = 0; q < BLOCK_NQ; ++q) {
+        const int e = tid + SOLVE_ROWS * q;
+        if ((e >> 4) < nb) {
+            if constexpr (ADD)
+                p[e] += s[REGS ? q : e];
+            else
+                p[e] = s[REGS ? q : e];
+        }
+    }
+}
+
 // Forward step of a panel: tasks as solve_fwd_kernel.  Y = X128 C_blk stays in LDS; wave
 // v forms ACC(64 x 16) = L(rows, blk) Y for rows r0 + 64 v .. (4 M tiles x 32 K steps,
 // each load four 128-byte runs; the second 64-column half of A goes out under the first
@@ -2474,24 +2503,12 @@ __global__ __launch_bounds__(SOLVE_ROWS) void solve_fwd_multi_kernel(SolvePlan P
             }
     };
     load_half(0);
-    const double* cblk = P.c + (int64_t)(c0 + k0) * SOLVE_RHS;
-#pragma unroll
-    for (int q = 0; q < SOLVE_PANEL / SOLVE_ROWS; ++q) {
-        const int e = tid + SOLVE_ROWS * q;
-        Cs[e] = (e >> 4) < nb ? cblk[e] : 0.0;
-    }
+    block_in(Cs, P.c + (int64_t)(c0 + k0) * SOLVE_RHS, nb);
     __syncthreads();
     diag_mfma_multi<false>(xa, nb, Cs, Ys);
     __syncthreads();
     if (r0 >= 0 && nb > PNB) load_half(1);  // in flight under the first half's products
-    if (t.w) {
-        double* __restrict__ yblk = P.y + (int64_t)(c0 + k0) * SOLVE_RHS;
-#pragma unroll
-        for (int q = 0; q < SOLVE_PANEL / SOLVE_ROWS; ++q) {
-            const int e = tid + SOLVE_ROWS * q;
-            if ((e >> 4) < nb) yblk[e] = Ys[e];
-        }
-    }
+    if (t.w) block_out(P.y + (int64_t)(c0 + k0) * SOLVE_RHS, Ys, nb);
     if (r0 < 0) return;
     double4_t acc[4];
 #pragma unroll
@@ -2563,15 +2580,17 @@ __global__ __launch_bounds__(GATHER_NT) void solve_fwd_gather_multi_kernel(Solve
     }
 }
 
-// Backward step of a panel, part 1: workgroup (s, k0, r0) leaves its partial
-// P(128 x 16) = -L(rows, blk)^T X(rows) in part[task].  L is loaded as in
+// Backward step of a panel, part 1, and part 1 of X = L^T Z (MUL): workgroup (s, k0, r0)
+// leaves its partial P(128 x 16) = -L(rows, blk)^T X(rows), X in P.c, or (MUL)
+// +L(rows, blk)^T Z(rows), Z in P.y, in part[task].  L is loaded as in
 // solve_gemv_kernel (thread = row, coalesced per column, all 128 columns in flight) and
 // transposed through LDS one 64-column half at a time, because in the MFMA layout the transposed operand would be
 // loaded in 32-byte runs.  Wave v owns rows r0 + 64 v ..: it reads back only what it
 // wrote (T[v]), holds its 64 rows of X as 16 B operands in registers, and the four
 // waves' 64 x 16 results are summed in wave order.
 constexpr int GEMV_LD = 64 + 4;  // column stride of T: 16 columns x 4 rows of an A read hit distinct banks
-__global__ __launch_bounds__(SOLVE_ROWS) void solve_gemv_multi_kernel(SolvePlan P, const int4* __restrict__ tasks) {
+template <bool MUL>
+__device__ __forceinline__ void gemv_multi(const SolvePlan& P, const int4* __restrict__ tasks) {
     __shared__ double T[SOLVE_ROWS / 64][PNB][GEMV_LD];  // T[v][j][row] = L(r0 + 64 v + row, j)
     static_assert(GEMV_LD >= SOLVE_RHS, "a wave's 64 x 16 result fits the start of its T[v]");
     const int4 t = tasks[blockIdx.x];
@@ -2586,11 +2605,12 @@ __global__ __launch_bounds__(SOLVE_ROWS) void solve_gemv_multi_kernel(SolvePlan 
     const int32_t* __restrict__ rows = P.rows + P.rows_ptr[s];
     const int r = r0 + tid;
     const bool live = r < m;
+    const double* x = MUL ? P.y : P.c;
     double bx[16];  // X(r0 + 64 v + 4 ks + kq, il); dead rows 0
 #pragma unroll
     for (int ks = 0; ks < 16; ++ks) {
         const int rr = r0 + 64 * wv + 4 * ks + kq;
-        bx[ks] = rr < m ? P.c[(int64_t)rows[rr] * SOLVE_RHS + il] : 0.0;
+        bx[ks] = rr < m ? x[(int64_t)rows[rr] * SOLVE_RHS + il] : 0.0;
     }
     const __amdgpu_buffer_rsrc_t rs = buf_rsrc(pan, (uint32_t)((int64_t)nb * m * 8));
     // both halves' loads go out at once (the second waits in registers)
@@ -2636,13 +2656,43 @@ __global__ __launch_bounds__(SOLVE_ROWS) void solve_gemv_multi_kernel(SolvePlan 
 #pragma unroll
         for (int q = 0; q < PNB * SOLVE_RHS / SOLVE_ROWS; ++q) {
             const int e = tid + SOLVE_ROWS * q;
-            out[e] = -(R[e] + R[W + e] + R[2 * W + e] + R[3 * W + e]);  // in wave order
+            const double sum = R[e] + R[W + e] + R[2 * W + e] + R[3 * W + e];  // in wave order
+            out[e] = MUL ? sum : -sum;
         }
     };
     half(0);
     if (nb > PNB) {
         __syncthreads();  // the first half's R fully read
         half(1);
+    }
+}
+
+__global__ __launch_bounds__(SOLVE_ROWS) void solve_gemv_multi_kernel(SolvePlan P, const int4* __restrict__ tasks) {
+    gemv_multi<false>(P, tasks);
+}
+
+// v (a thread's BLOCK_NQ entries of a 128 x 16 block, as block_in<true> lays them out) plus
+// the block's ng partials in task order, DIAG_PF tasks (x BLOCK_NQ entries per thread) in
+// flight at a time; rows past nb stay as they are (dead parts of a partial are never read)
+static_assert(SOLVE_ROWS == 256, "the diagonal kernels move their blocks with block_in / block_out");
+__device__ __forceinline__ void diag_add_parts(const double* __restrict__ part, int ng, int nb, double (&v)[BLOCK_NQ]) {
+    constexpr int DIAG_PF = 8;
+    const int tid = threadIdx.x;
+    for (int g0 = 0; g0 < ng; g0 += DIAG_PF) {
+        double pv[DIAG_PF][BLOCK_NQ];
+#pragma unroll
+        for (int u = 0; u < DIAG_PF; ++u)
+#pragma unroll
+            for (int q = 0; q < BLOCK_NQ; ++q) {
+                const int e = tid + 256 * q;
+                pv[u][q] = (g0 + u < ng && (e >> 4) < nb) ? part[(int64_t)(g0 + u) * SOLVE_PANEL + e] : 0.0;
+            }
+#pragma unroll
+        for (int u = 0; u < DIAG_PF; ++u)
+            if (g0 + u < ng) {
+#pragma unroll
+                for (int q = 0; q < BLOCK_NQ; ++q) v[q] += pv[u][q];
+            }
     }
 }
 
@@ -2661,42 +2711,15 @@ __global__ __launch_bounds__(256) void solve_diag_multi_kernel(SolvePlan P, cons
     double* __restrict__ cblk = P.c + (int64_t)(c0 + k0) * SOLVE_RHS;
     DiagA xa;
     diag_load_multi<true>(blk, m, nb, xa);
-    // C_blk plus the partials in task order, DIAG_PF tasks (x 8 entries per thread) in
-    // flight at a time; rows past nb stay 0 (dead parts of a partial are never read)
-    constexpr int NQ = SOLVE_PANEL / 256, DIAG_PF = 8;
-    double v[NQ];
+    double v[BLOCK_NQ];  // rows past nb stay 0
+    block_in<true>(v, cblk, nb);
+    diag_add_parts(P.part + (int64_t)t.z * SOLVE_PANEL, t.w, nb, v);
 #pragma unroll
-    for (int q = 0; q < NQ; ++q) {
-        const int e = tid + 256 * q;
-        v[q] = (e >> 4) < nb ? cblk[e] : 0.0;
-    }
-    const double* __restrict__ part = P.part + (int64_t)t.z * SOLVE_PANEL;
-    for (int g0 = 0; g0 < t.w; g0 += DIAG_PF) {
-        double pv[DIAG_PF][NQ];
-#pragma unroll
-        for (int u = 0; u < DIAG_PF; ++u)
-#pragma unroll
-            for (int q = 0; q < NQ; ++q) {
-                const int e = tid + 256 * q;
-                pv[u][q] = (g0 + u < t.w && (e >> 4) < nb) ? part[(int64_t)(g0 + u) * SOLVE_PANEL + e] : 0.0;
-            }
-#pragma unroll
-        for (int u = 0; u < DIAG_PF; ++u)
-            if (g0 + u < t.w) {
-#pragma unroll
-                for (int q = 0; q < NQ; ++q) v[q] += pv[u][q];
-            }
-    }
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) Cs[tid + 256 * q] = v[q];
+    for (int q = 0; q < BLOCK_NQ; ++q) Cs[tid + 256 * q] = v[q];
     __syncthreads();
     diag_mfma_multi<true>(xa, nb, Cs, Ys);
     __syncthreads();
-#pragma unroll
-    for (int q = 0; q < SOLVE_PANEL / 256; ++q) {
-        const int e = tid + 256 * q;
-        if ((e >> 4) < nb) cblk[e] = Ys[e];
-    }
+    block_out(cblk, Ys, nb);
 }
 
 // c (16-wide rows, internal order) <- io (n x 16 column-major, caller's order) or back;
@@ -2743,7 +2766,9 @@ __global__ __launch_bounds__(256) void permute_multi_kernel(double* __restrict__
 // ACC(64 x 16) = L(rows, blk) Z_blk for rows r0 + 64 v .. and adds it to c (rows < w:
 // the front's own later pivots) or to the front's u (its contribution-block rows, which
 // the parent's gather adds in child order); the writer also adds L_blk Z_blk (lower
-// triangular) to c_blk.  c and u start at zero.
+// triangular) to c_blk.  c and u start at zero.  load_half, mfma_half and the scatter repeat
+// solve_fwd_multi_kernel's on purpose: behind shared device functions the compiler
+// scheduled this kernel differently and X = L Z at 64^3 measured 0.2 % slower.
 __global__ __launch_bounds__(SOLVE_ROWS) void mul_l_multi_kernel(SolvePlan P, const int4* __restrict__ tasks) {
     __shared__ double Zs[SOLVE_PANEL], Ys[SOLVE_PANEL];
     const int4 t = tasks[blockIdx.x];
@@ -2771,24 +2796,14 @@ __global__ __launch_bounds__(SOLVE_ROWS) void mul_l_multi_kernel(SolvePlan P, co
             }
     };
     load_half(0);
-    const double* zblk = P.y + (int64_t)(c0 + k0) * SOLVE_RHS;
-#pragma unroll
-    for (int q = 0; q < SOLVE_PANEL / SOLVE_ROWS; ++q) {
-        const int e = tid + SOLVE_ROWS * q;
-        Zs[e] = (e >> 4) < nb ? zblk[e] : 0.0;
-    }
+    block_in(Zs, P.y + (int64_t)(c0 + k0) * SOLVE_RHS, nb);
     __syncthreads();
     if (t.w) {  // workgroup-uniform
         diag_mfma_multi<false, false>(la, nb, Zs, Ys);
         __syncthreads();
         // the block's rows of c: earlier steps of the front and the gather have added to
         // them in earlier launches, no other workgroup of this step does
-        double* __restrict__ cblk = P.c + (int64_t)(c0 + k0) * SOLVE_RHS;
-#pragma unroll
-        for (int q = 0; q < SOLVE_PANEL / SOLVE_ROWS; ++q) {
-            const int e = tid + SOLVE_ROWS * q;
-            if ((e >> 4) < nb) cblk[e] += Ys[e];
-        }
+        block_out<false, true>(P.c + (int64_t)(c0 + k0) * SOLVE_RHS, Ys, nb);
     }
     if (r0 < 0) return;
     if (nb > PNB) load_half(1);  // in flight under the first half's products
@@ -2829,81 +2844,9 @@ __global__ __launch_bounds__(SOLVE_ROWS) void mul_l_multi_kernel(SolvePlan P, co
         }
 }
 
-// X = L^T Z, part 1: workgroup (s, k0, r0) leaves its partial P(128 x 16) = L(rows,
-// blk)^T Z(rows) in part[task]: solve_gemv_multi_kernel with Z read from P.y and the
-// opposite sign (L transposed through LDS one 64-column half at a time, wave v owning
-// rows r0 + 64 v .., the four waves' results summed in wave order).
+// X = L^T Z, part 1: gemv_multi with Z read from P.y and the sum as it is.
 __global__ __launch_bounds__(SOLVE_ROWS) void mul_lt_gemv_multi_kernel(SolvePlan P, const int4* __restrict__ tasks) {
-    __shared__ double T[SOLVE_ROWS / 64][PNB][GEMV_LD];  // T[v][j][row] = L(r0 + 64 v + row, j)
-    const int4 t = tasks[blockIdx.x];
-    const int s = t.x, k0 = t.y, r0 = t.z;
-    const int tid = threadIdx.x, lane = tid & 63, wv = wave_id();
-    const int il = lane & 15, kq = lane >> 4;
-    const int c0 = P.sn_start[s];
-    const int w = P.sn_start[s + 1] - c0;
-    const int m = P.sn_m[s];
-    const int nb = min(SOLVE_NB, w - k0);
-    const double* __restrict__ pan = P.panel_pool + P.panel_off[s] + (int64_t)k0 * m;
-    const int32_t* __restrict__ rows = P.rows + P.rows_ptr[s];
-    const int r = r0 + tid;
-    const bool live = r < m;
-    double bz[16];  // Z(r0 + 64 v + 4 ks + kq, il); dead rows 0
-#pragma unroll
-    for (int ks = 0; ks < 16; ++ks) {
-        const int rr = r0 + 64 * wv + 4 * ks + kq;
-        bz[ks] = rr < m ? P.y[(int64_t)rows[rr] * SOLVE_RHS + il] : 0.0;
-    }
-    const __amdgpu_buffer_rsrc_t rs = buf_rsrc(pan, (uint32_t)((int64_t)nb * m * 8));
-    double v[2][PNB];  // both halves' loads go out at once (the second waits in registers)
-#pragma unroll
-    for (int h = 0; h < 2; ++h)
-#pragma unroll
-        for (int q = 0; q < PNB; ++q) {
-            const int col = h * PNB + q;
-            v[h][q] = buf_ld(rs, (live & (col < nb)) ? (col * m + r) * 8 : BUF_DEAD, 0);
-        }
-    // R[v][j][16]: wave v's result, over the start of its own T[v] once its products are done
-    constexpr int W = PNB * GEMV_LD;
-    double* R = &T[0][0][0];
-    auto half = [&](int h) {
-#pragma unroll
-        for (int q = 0; q < PNB; ++q) T[wv][q][lane] = v[h][q];
-        __syncthreads();
-        double4_t acc[4];
-#pragma unroll
-        for (int I = 0; I < 4; ++I) acc[I] = double4_t {0.0, 0.0, 0.0, 0.0};
-        // tiles past nb and 16-row groups past m are skipped (wave-uniform; zeros)
-#pragma unroll
-        for (int I = 0; I < 4; ++I) {
-            if (h * PNB + 16 * I >= nb) continue;
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                if (r0 + 64 * wv + 16 * g >= m) continue;
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const int ks = 4 * g + u;
-                    acc[I] = __builtin_amdgcn_mfma_f64_16x16x4f64(T[wv][16 * I + il][4 * ks + kq], bz[ks], acc[I], 0, 0,
-                                                                  0);
-                }
-            }
-        }
-#pragma unroll
-        for (int I = 0; I < 4; ++I)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) R[wv * W + (16 * I + kq + 4 * g) * SOLVE_RHS + il] = acc[I][g];
-        __syncthreads();
-        double* __restrict__ out = P.part + ((int64_t)blockIdx.x * SOLVE_NB + h * PNB) * SOLVE_RHS;
-#pragma unroll
-        for (int q = 0; q < PNB * SOLVE_RHS / SOLVE_ROWS; ++q) {
-            const int e = tid + SOLVE_ROWS * q;
-            out[e] = R[e] + R[W + e] + R[2 * W + e] + R[3 * W + e];  // in wave order
-        }
-    };
-    half(0);
-    if (nb > PNB) {
-        __syncthreads();  // the first half's R fully read
-        half(1);
-    }
+    gemv_multi<true>(P, tasks);
 }
 
 // X = L^T Z, part 2: X_blk = L_blk^T Z_blk plus the block's partials in task order, into
@@ -2922,42 +2865,15 @@ __global__ __launch_bounds__(256) void mul_lt_diag_multi_kernel(SolvePlan P, con
     double* __restrict__ cblk = P.c + (int64_t)(c0 + k0) * SOLVE_RHS;
     DiagA la;
     diag_load_multi<true, false>(blk, m, nb, la);
-    constexpr int NQ = SOLVE_PANEL / 256, DIAG_PF = 8;
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) {
-        const int e = tid + 256 * q;
-        Zs[e] = (e >> 4) < nb ? zblk[e] : 0.0;
-    }
+    block_in(Zs, zblk, nb);
     __syncthreads();
     diag_mfma_multi<true, false>(la, nb, Zs, Ys);
     __syncthreads();
-    // the partials in task order, DIAG_PF tasks in flight at a time (dead parts of a
-    // partial are never read)
-    double v[NQ];
+    double v[BLOCK_NQ];
 #pragma unroll
-    for (int q = 0; q < NQ; ++q) v[q] = Ys[tid + 256 * q];
-    const double* __restrict__ part = P.part + (int64_t)t.z * SOLVE_PANEL;
-    for (int g0 = 0; g0 < t.w; g0 += DIAG_PF) {
-        double pv[DIAG_PF][NQ];
-#pragma unroll
-        for (int u = 0; u < DIAG_PF; ++u)
-#pragma unroll
-            for (int q = 0; q < NQ; ++q) {
-                const int e = tid + 256 * q;
-                pv[u][q] = (g0 + u < t.w && (e >> 4) < nb) ? part[(int64_t)(g0 + u) * SOLVE_PANEL + e] : 0.0;
-            }
-#pragma unroll
-        for (int u = 0; u < DIAG_PF; ++u)
-            if (g0 + u < t.w) {
-#pragma unroll
-                for (int q = 0; q < NQ; ++q) v[q] += pv[u][q];
-            }
-    }
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) {
-        const int e = tid + 256 * q;
-        if ((e >> 4) < nb) cblk[e] = v[q];
-    }
+    for (int q = 0; q < BLOCK_NQ; ++q) v[q] = Ys[tid + 256 * q];
+    diag_add_parts(P.part + (int64_t)t.z * SOLVE_PANEL, t.w, nb, v);
+    block_out<true>(cblk, v, nb);
 }
 
 // log det A = 2 sum_j log L(j, j): the n diagonal entries straight from the panels
@@ -3004,24 +2920,6 @@ __global__ __launch_bounds__(LOGDET_NT) void logdet_final_kernel(const double* _
     if (threadIdx.x == 0) out[0] = 2.0 * sum;
 }
 
-hipError_t launch_mul_l_multi(const SolvePlan& P, const int4* tasks, int count, hipStream_t st) {
-    if (count <= 0) return hipSuccess;
-    hipLaunchKernelGGL(mul_l_multi_kernel, dim3(count), dim3(SOLVE_ROWS), 0, st, P, tasks);
-    return hipGetLastError();
-}
-
-hipError_t launch_mul_lt_gemv_multi(const SolvePlan& P, const int4* tasks, int count, hipStream_t st) {
-    if (count <= 0) return hipSuccess;
-    hipLaunchKernelGGL(mul_lt_gemv_multi_kernel, dim3(count), dim3(SOLVE_ROWS), 0, st, P, tasks);
-    return hipGetLastError();
-}
-
-hipError_t launch_mul_lt_diag_multi(const SolvePlan& P, const int4* tasks, int count, hipStream_t st) {
-    if (count <= 0) return hipSuccess;
-    hipLaunchKernelGGL(mul_lt_diag_multi_kernel, dim3(count), dim3(256), 0, st, P, tasks);
-    return hipGetLastError();
-}
-
 hipError_t launch_logdet(const SolvePlan& P, int ns, int64_t n, double* part, double* out, hipStream_t st) {
     const int np = (int)((n + LOGDET_NT - 1) / LOGDET_NT);
     if (np > 0) hipLaunchKernelGGL(logdet_partial_kernel, dim3(np), dim3(LOGDET_NT), 0, st, P, ns, (int)n, part);
@@ -3029,28 +2927,41 @@ hipError_t launch_logdet(const SolvePlan& P, int ns, int64_t n, double* part, do
     return hipGetLastError();
 }
 
-hipError_t launch_solve_fwd_multi(const SolvePlan& P, const int4* tasks, int count, hipStream_t st) {
+// One workgroup (or GATHER_SPLIT) per task of a list; an empty list is no launch.
+template <class K, class T>
+static hipError_t launch_tasks(K kernel, dim3 grid, int nt, const SolvePlan& P, const T* tasks, int count,
+                               hipStream_t st) {
     if (count <= 0) return hipSuccess;
-    hipLaunchKernelGGL(solve_fwd_multi_kernel, dim3(count), dim3(SOLVE_ROWS), 0, st, P, tasks);
+    hipLaunchKernelGGL(kernel, grid, dim3(nt), 0, st, P, tasks);
     return hipGetLastError();
+}
+
+hipError_t launch_mul_l_multi(const SolvePlan& P, const int4* tasks, int count, hipStream_t st) {
+    return launch_tasks(mul_l_multi_kernel, dim3(count), SOLVE_ROWS, P, tasks, count, st);
+}
+
+hipError_t launch_mul_lt_gemv_multi(const SolvePlan& P, const int4* tasks, int count, hipStream_t st) {
+    return launch_tasks(mul_lt_gemv_multi_kernel, dim3(count), SOLVE_ROWS, P, tasks, count, st);
+}
+
+hipError_t launch_mul_lt_diag_multi(const SolvePlan& P, const int4* tasks, int count, hipStream_t st) {
+    return launch_tasks(mul_lt_diag_multi_kernel, dim3(count), 256, P, tasks, count, st);
+}
+
+hipError_t launch_solve_fwd_multi(const SolvePlan& P, const int4* tasks, int count, hipStream_t st) {
+    return launch_tasks(solve_fwd_multi_kernel, dim3(count), SOLVE_ROWS, P, tasks, count, st);
 }
 
 hipError_t launch_solve_fwd_gather_multi(const SolvePlan& P, const int32_t* fronts, int count, hipStream_t st) {
-    if (count <= 0) return hipSuccess;
-    hipLaunchKernelGGL(solve_fwd_gather_multi_kernel, dim3(count, GATHER_SPLIT), dim3(GATHER_NT), 0, st, P, fronts);
-    return hipGetLastError();
+    return launch_tasks(solve_fwd_gather_multi_kernel, dim3(count, GATHER_SPLIT), GATHER_NT, P, fronts, count, st);
 }
 
 hipError_t launch_solve_gemv_multi(const SolvePlan& P, const int4* tasks, int count, hipStream_t st) {
-    if (count <= 0) return hipSuccess;
-    hipLaunchKernelGGL(solve_gemv_multi_kernel, dim3(count), dim3(SOLVE_ROWS), 0, st, P, tasks);
-    return hipGetLastError();
+    return launch_tasks(solve_gemv_multi_kernel, dim3(count), SOLVE_ROWS, P, tasks, count, st);
 }
 
 hipError_t launch_solve_diag_multi(const SolvePlan& P, const int4* tasks, int count, hipStream_t st) {
-    if (count <= 0) return hipSuccess;
-    hipLaunchKernelGGL(solve_diag_multi_kernel, dim3(count), dim3(256), 0, st, P, tasks);
-    return hipGetLastError();
+    return launch_tasks(solve_diag_multi_kernel, dim3(count), 256, P, tasks, count, st);
 }
 
 hipError_t launch_permute_multi(double* c, double* io, const int32_t* perm, int64_t n, bool scatter,

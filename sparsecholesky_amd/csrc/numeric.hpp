@@ -339,20 +339,18 @@ struct Numeric {
     int4* d_sfwd = nullptr;  // fused forward steps (s, k0, r0, writer)
     int32_t* d_post = nullptr;
     double* d_sbuf = nullptr;  // host-interface staging (b in, x out)
-    bool solve_eager = false;          // debug: launch the sweeps directly instead of the graph
-    hipGraph_t solve_graph = nullptr;  // both sweeps captured once (b in / x out through d_sbuf)
-    hipGraphExec_t solve_gexec = nullptr;
-    // panel solves (SOLVE_RHS right-hand sides): the plan's 16-wide buffers, allocated at
-    // the first multi solve, and the panel sweeps captured over d_mbuf's io panel
+    bool solve_eager = false;  // debug: launch the sweeps directly instead of the graphs
+    // panel family (SOLVE_RHS right-hand sides): the plan's 16-wide buffers, allocated at
+    // the first panel sweep
     bool multi_ready = false;
     SolvePlan SPM {};
     int64_t solve_max_g = 1;           // most GEMV workgroups in one backward step
     double* d_mbuf = nullptr;          // io (n x SOLVE_RHS column-major), c, y (SOLVE_RHS-wide rows)
-    hipGraph_t solve_multi_graph = nullptr;
-    hipGraphExec_t solve_multi_gexec = nullptr;
-    // factor operators (numeric_apply_*): the etree postorder alone (d_post itself when no
-    // fill-reducing permutation is in effect), uploaded at the first apply, and one lazily
-    // captured graph per family (0 single vector, 1 panel) and op (sc_factor_op)
+    // the solves and the factor operators (numeric_apply_*): the etree postorder alone
+    // (d_post itself when no fill-reducing permutation is in effect), uploaded at the first
+    // L-level op, and one lazily captured graph per family (0 single vector, in and out
+    // through d_sbuf; 1 panel, through d_mbuf's io) and op (sc_factor_op; the solves are
+    // SC_OP_SOLVE_A)
     static constexpr int APPLY_OPS = 7;
     int32_t* d_etpost = nullptr;
     hipGraph_t apply_graph[2][APPLY_OPS] = {};
@@ -461,7 +459,7 @@ int64_t numeric_solve_host_multi(Numeric& N, int32_t nrhs, const double* B, int6
 // Factor operators (op: sc_factor_op; L in the numbering of numeric_export, the order of
 // P A P^T): X = op(B).  The single-vector entry points run the single-vector kernels for
 // the half solves; the products have panel kernels only, so a single vector travels as a
-// panel of one column.  SC_OP_SOLVE_A is numeric_solve_*.  Buffers, status, ordering and
+// panel of one column.  numeric_solve_* are SC_OP_SOLVE_A.  Buffers, status, ordering and
 // collective rules of the solves; x may be b.
 int64_t numeric_apply_device(Numeric& N, int32_t op, const double* d_b, double* d_x);
 int64_t numeric_apply_host(Numeric& N, int32_t op, const double* b, double* x);
@@ -542,7 +540,7 @@ int64_t debug_updown_block(double* dF, int m, int w, int k0, double* dW, int sig
 int64_t debug_solve_step(double* dF, int m, int w, int k0, int op, int width, double* dC, double* dY, double* dU);
 int64_t debug_solve_gather(int width, int w, int mb, int nchild, const int64_t* rel_ptr, const int32_t* relind,
                            const double* dUc, double* dC, double* dU);
-// Destroys the captured solve and apply graphs (they point at one panel pool).
+// Destroys the captured graphs of the solves and operators (they point at one panel pool).
 void numeric_drop_solve_graphs(Numeric& N);
 int64_t debug_syrk(double* dC, int ldc, const double* dA, int lda, int M, int N, int K);
 // debug_syrk on the instance the caller names: bt 64 / 128, lean (64 only), tag, epi; no

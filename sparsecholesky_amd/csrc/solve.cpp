@@ -203,19 +203,16 @@ static int64_t solve_build(Numeric& N) {
 }
 
 void numeric_drop_solve_graphs(Numeric& N) {
-    auto drop = [](hipGraph_t& g, hipGraphExec_t& x) {
-        if (x) (void)hipGraphExecDestroy(x);
-        if (g) (void)hipGraphDestroy(g);
-        x = nullptr;
-        g = nullptr;
-    };
-    drop(N.solve_graph, N.solve_gexec);
-    drop(N.solve_multi_graph, N.solve_multi_gexec);
     for (int f = 0; f < 2; ++f)
-        for (int op = 0; op < Numeric::APPLY_OPS; ++op) drop(N.apply_graph[f][op], N.apply_gexec[f][op]);
+        for (int op = 0; op < Numeric::APPLY_OPS; ++op) {
+            if (N.apply_gexec[f][op]) (void)hipGraphExecDestroy(N.apply_gexec[f][op]);
+            if (N.apply_graph[f][op]) (void)hipGraphDestroy(N.apply_graph[f][op]);
+            N.apply_gexec[f][op] = nullptr;
+            N.apply_graph[f][op] = nullptr;
+        }
 }
 
-// What both solves start with: the whole factor in gpanel (multi-rank: collective), the
+// What every sweep starts with: the whole factor in gpanel (multi-rank: collective), the
 // plan built, and the captured sweeps dropped when they point at another panel pool.
 int64_t solve_prepare(Numeric& N) {
     HIP_TRY(hipSetDevice(N.device));
@@ -229,79 +226,8 @@ int64_t solve_prepare(Numeric& N) {
     return SC_OK;
 }
 
-int64_t numeric_solve_device(Numeric& N, const double* d_b, double* d_x) {
-    if (!N.factored) return SC_ERR_STATE;
-    const int64_t st = numeric_status(N);
-    if (st != SC_OK) return st;
-    TRY(solve_prepare(N));
-    const int64_t n = N.S->n;
-    if (n == 0) return SC_OK;
-    hipStream_t s0 = N.stream;
-    // the graph reads b from and writes x to the handle's own vector io = d_sbuf[0, n),
-    // so it is captured once, whatever buffers the caller passes
-    double* io = N.d_sbuf;
-    auto sweeps = [&]() -> hipError_t {
-        hipError_t e = launch_permute(N.SP.c, io, N.d_post, n, false, s0);
-        if (e == hipSuccess) e = hipMemsetAsync(N.SP.u, 0, (size_t)std::max<int64_t>(N.u_total, 1) * sizeof(double), s0);
-        // forward: per level the children's u gathered, then one fused launch per step
-        // (y to SP.y), then y -> c
-        for (size_t i = 0; e == hipSuccess && i < N.solve_steps.size(); ++i) {
-            const Numeric::SolveStep& t = N.solve_steps[i];
-            e = launch_solve_fwd_gather(N.SP, N.d_sgather + t.gaoff, t.gacount, s0);
-            if (e == hipSuccess) e = launch_solve_fwd(N.SP, N.d_sfwd + t.foff, t.fcount, s0);
-        }
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(N.SP.c, N.SP.y, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, s0);
-        for (size_t i = N.solve_steps.size(); e == hipSuccess && i-- > 0;) {
-            const Numeric::SolveStep& t = N.solve_steps[i];
-            e = launch_solve_gemv(N.SP, N.d_sgemv + t.goff, t.gcount, s0);
-            if (e == hipSuccess) e = launch_solve_diag(N.SP, N.d_sdiag + t.doff, t.dcount, s0);
-        }
-        if (e == hipSuccess) e = launch_permute(io, N.SP.c, N.d_post, n, true, s0);
-        return e;
-    };
-    if (!N.solve_gexec && !N.solve_eager) {
-        // ~700 dependent steps per sweep at 128^3: replayed as one hipGraph
-        HIP_TRY(hipStreamBeginCapture(s0, hipStreamCaptureModeThreadLocal));
-        hipError_t e = sweeps();
-        hipGraph_t g = nullptr;
-        hipError_t e2 = hipStreamEndCapture(s0, &g);
-        HIP_TRY(e);
-        HIP_TRY(e2);
-        N.solve_graph = g;
-        HIP_TRY(hipGraphInstantiate(&N.solve_gexec, g, nullptr, nullptr, 0));
-    }
-    if (N.inv_gen != N.factor_gen) {  // inverses of the diagonal blocks, once per factorization
-        HIP_TRY(launch_solve_inv(N.SP, N.d_sinv, N.n_sinv, N.d_sinv2, N.n_sinv2, s0));
-        N.inv_gen = N.factor_gen;
-    }
-    const size_t nb = (size_t)n * sizeof(double);
-    if (d_b != io) HIP_TRY(hipMemcpyAsync(io, d_b, nb, hipMemcpyDeviceToDevice, s0));
-    if (N.solve_eager)
-        HIP_TRY(sweeps());
-    else
-        HIP_TRY(hipGraphLaunch(N.solve_gexec, s0));
-    if (d_x != io) HIP_TRY(hipMemcpyAsync(d_x, io, nb, hipMemcpyDeviceToDevice, s0));
-    HIP_TRY(hipStreamSynchronize(s0));
-    return SC_OK;
-}
-
-int64_t numeric_solve_host(Numeric& N, const double* b, double* x) {
-    if (!N.factored) return SC_ERR_STATE;
-    const int64_t st = numeric_status(N);
-    if (st != SC_OK) return st;
-    HIP_TRY(hipSetDevice(N.device));
-    if (!N.solve_ready) TRY(solve_build(N));
-    const size_t nb = (size_t)N.S->n * sizeof(double);
-    if (nb == 0) return SC_OK;
-    HIP_TRY(hipMemcpy(N.d_sbuf, b, nb, hipMemcpyHostToDevice));
-    TRY(numeric_solve_device(N, N.d_sbuf, N.d_sbuf));
-    HIP_TRY(hipMemcpy(x, N.d_sbuf, nb, hipMemcpyDeviceToHost));
-    return SC_OK;
-}
-
-// ---------------- panel solves (SOLVE_RHS right-hand sides per sweep) ----------------
-// The 16-wide twins of the plan's work buffers, at the first multi solve only.
+// ---------------- panel family (SOLVE_RHS right-hand sides per sweep) ----------------
+// The 16-wide twins of the plan's work buffers, at the first panel sweep only.
 static int64_t solve_multi_build(Numeric& N) {
     const int64_t n1 = std::max<int64_t>(N.S->n, 1);
     void* p = nullptr;
@@ -316,82 +242,6 @@ static int64_t solve_multi_build(Numeric& N) {
     N.SPM.part = (double*)p;
     N.multi_ready = true;
     return SC_OK;
-}
-
-// in / out: the copy kinds of the caller's B and X (device or host memory)
-static int64_t solve_multi(Numeric& N, int32_t nrhs, const double* B, int64_t ldb, double* X, int64_t ldx,
-                           hipMemcpyKind in, hipMemcpyKind out) {
-    if (!N.factored) return SC_ERR_STATE;
-    const int64_t st = numeric_status(N);
-    if (st != SC_OK) return st;
-    TRY(solve_prepare(N));
-    const int64_t n = N.S->n;
-    if (n == 0 || nrhs == 0) return SC_OK;
-    if (!N.multi_ready) TRY(solve_multi_build(N));
-    hipStream_t s0 = N.stream;
-    const SolvePlan& P = N.SPM;
-    // the graph solves the handle's own panel io = d_mbuf[0, 16 n) (column-major, the
-    // caller's order) in place, so it is captured once, whatever the caller passes
-    double* io = N.d_mbuf;
-    const size_t wide = (size_t)SOLVE_RHS * sizeof(double);
-    auto sweeps = [&]() -> hipError_t {
-        hipError_t e = launch_permute_multi(P.c, io, N.d_post, n, false, s0);
-        if (e == hipSuccess) e = hipMemsetAsync(P.u, 0, (size_t)std::max<int64_t>(N.u_total, 1) * wide, s0);
-        for (size_t i = 0; e == hipSuccess && i < N.solve_steps.size(); ++i) {
-            const Numeric::SolveStep& t = N.solve_steps[i];
-            e = launch_solve_fwd_gather_multi(P, N.d_sgather + t.gaoff, t.gacount, s0);
-            if (e == hipSuccess) e = launch_solve_fwd_multi(P, N.d_sfwd + t.foff, t.fcount, s0);
-        }
-        if (e == hipSuccess) e = hipMemcpyAsync(P.c, P.y, (size_t)n * wide, hipMemcpyDeviceToDevice, s0);
-        for (size_t i = N.solve_steps.size(); e == hipSuccess && i-- > 0;) {
-            const Numeric::SolveStep& t = N.solve_steps[i];
-            e = launch_solve_gemv_multi(P, N.d_sgemv + t.goff, t.gcount, s0);
-            if (e == hipSuccess) e = launch_solve_diag_multi(P, N.d_sdiag + t.doff, t.dcount, s0);
-        }
-        if (e == hipSuccess) e = launch_permute_multi(P.c, io, N.d_post, n, true, s0);
-        return e;
-    };
-    if (!N.solve_multi_gexec && !N.solve_eager) {  // a single-stream chain, like the single-vector graph
-        HIP_TRY(hipStreamBeginCapture(s0, hipStreamCaptureModeThreadLocal));
-        hipError_t e = sweeps();
-        hipGraph_t g = nullptr;
-        hipError_t e2 = hipStreamEndCapture(s0, &g);
-        HIP_TRY(e);
-        HIP_TRY(e2);
-        N.solve_multi_graph = g;
-        HIP_TRY(hipGraphInstantiate(&N.solve_multi_gexec, g, nullptr, nullptr, 0));
-    }
-    if (N.inv_gen != N.factor_gen) {  // shared with the single-vector solve
-        HIP_TRY(launch_solve_inv(N.SP, N.d_sinv, N.n_sinv, N.d_sinv2, N.n_sinv2, s0));
-        N.inv_gen = N.factor_gen;
-    }
-    const size_t colb = (size_t)n * sizeof(double);
-    for (int32_t j0 = 0; j0 < nrhs; j0 += SOLVE_RHS) {
-        const int nr = std::min<int32_t>(SOLVE_RHS, nrhs - j0);
-        HIP_TRY(hipMemcpy2DAsync(io, colb, B + (int64_t)j0 * ldb, (size_t)ldb * sizeof(double), colb, (size_t)nr, in,
-                                 s0));
-        // a partial panel: true zero columns, never the caller's memory
-        if (nr < SOLVE_RHS) HIP_TRY(hipMemsetAsync(io + (int64_t)nr * n, 0, (size_t)(SOLVE_RHS - nr) * colb, s0));
-        if (N.solve_eager)
-            HIP_TRY(sweeps());
-        else
-            HIP_TRY(hipGraphLaunch(N.solve_multi_gexec, s0));
-        HIP_TRY(hipMemcpy2DAsync(X + (int64_t)j0 * ldx, (size_t)ldx * sizeof(double), io, colb, colb, (size_t)nr, out,
-                                 s0));
-        // host memory: one panel staged at a time
-        if (out != hipMemcpyDeviceToDevice) HIP_TRY(hipStreamSynchronize(s0));
-    }
-    HIP_TRY(hipStreamSynchronize(s0));
-    return SC_OK;
-}
-
-int64_t numeric_solve_device_multi(Numeric& N, int32_t nrhs, const double* d_B, int64_t ldb, double* d_X,
-                                   int64_t ldx) {
-    return solve_multi(N, nrhs, d_B, ldb, d_X, ldx, hipMemcpyDeviceToDevice, hipMemcpyDeviceToDevice);
-}
-
-int64_t numeric_solve_host_multi(Numeric& N, int32_t nrhs, const double* B, int64_t ldb, double* X, int64_t ldx) {
-    return solve_multi(N, nrhs, B, ldb, X, ldx, hipMemcpyHostToDevice, hipMemcpyDeviceToHost);
 }
 
 // ---------------- factor operators (sc_factor_op) ----------------
@@ -413,19 +263,128 @@ int64_t apply_prepare(Numeric& N) {
     return SC_OK;
 }
 
-// Runs sweeps() on the handle's stream: eagerly (sc_debug_solve_eager), or as the op's
-// graph, captured at its first use (a single-stream chain, like the solves' graphs).
-template <class F>
-static int64_t apply_run(Numeric& N, int family, int32_t op, F&& sweeps) {
+// What every entry point below starts with: a factor in good standing, then the plan
+// (etpost: with the etree postorder, for the L-level ops).
+static int64_t solve_begin(Numeric& N, bool etpost) {
+    if (!N.factored) return SC_ERR_STATE;
+    const int64_t st = numeric_status(N);
+    if (st != SC_OK) return st;
+    return etpost ? apply_prepare(N) : solve_prepare(N);
+}
+
+int64_t solve_inverses(Numeric& N) {
+    if (N.inv_gen != N.factor_gen) {  // once per factorization
+        HIP_TRY(launch_solve_inv(N.SP, N.d_sinv, N.n_sinv, N.d_sinv2, N.n_sinv2, N.stream));
+        N.inv_gen = N.factor_gen;
+    }
+    return SC_OK;
+}
+
+// The launchers of a family's sweeps: 0 the single-vector kernels on N.SP, io the vector
+// d_sbuf[0, n); 1 the panel kernels on N.SPM, io the panel d_mbuf[0, 16 n) (column-major,
+// the caller's order).  permute: c <- io gathered by perm, or io <- c scattered.
+using StepFn = hipError_t (*)(const SolvePlan&, const int4*, int, hipStream_t);
+struct SweepFamily {
+    hipError_t (*permute)(double* c, double* io, const int32_t* perm, int64_t n, bool scatter, hipStream_t st);
+    hipError_t (*gather)(const SolvePlan&, const int32_t*, int, hipStream_t);
+    StepFn fwd, gemv, diag;
+};
+static hipError_t permute_single(double* c, double* io, const int32_t* perm, int64_t n, bool scatter, hipStream_t st) {
+    return scatter ? launch_permute(io, c, perm, n, true, st) : launch_permute(c, io, perm, n, false, st);
+}
+static const SweepFamily SWEEP[2] = {
+    {permute_single, launch_solve_fwd_gather, launch_solve_fwd, launch_solve_gemv, launch_solve_diag},
+    {launch_permute_multi, launch_solve_fwd_gather_multi, launch_solve_fwd_multi, launch_solve_gemv_multi,
+     launch_solve_diag_multi}};
+
+// Bottom-up pass: per level the children's u gathered, then one launch of step per
+// 128-column step on the forward tasks.
+static hipError_t sweep_up(const Numeric& N, const SolvePlan& P, const SweepFamily& K, StepFn step, hipStream_t s0) {
+    hipError_t e = hipSuccess;
+    for (size_t i = 0; e == hipSuccess && i < N.solve_steps.size(); ++i) {
+        const Numeric::SolveStep& t = N.solve_steps[i];
+        e = K.gather(P, N.d_sgather + t.gaoff, t.gacount, s0);
+        if (e == hipSuccess) e = step(P, N.d_sfwd + t.foff, t.fcount, s0);
+    }
+    return e;
+}
+
+// Per step the partials over the rows below a block (gemv), then the diagonal blocks
+// (diag): the steps last to first (top-down), or, up, in the forward order.
+static hipError_t sweep_blocks(const Numeric& N, const SolvePlan& P, StepFn gemv, StepFn diag, bool up,
+                               hipStream_t s0) {
+    const size_t ns = N.solve_steps.size();
+    hipError_t e = hipSuccess;
+    for (size_t i = 0; e == hipSuccess && i < ns; ++i) {
+        const Numeric::SolveStep& t = N.solve_steps[up ? i : ns - 1 - i];
+        e = gemv(P, N.d_sgemv + t.goff, t.gcount, s0);
+        if (e == hipSuccess) e = diag(P, N.d_sdiag + t.doff, t.dcount, s0);
+    }
+    return e;
+}
+
+// Enqueues op on the handle's stream, from the family's io and back into it.  The full
+// solve permutes by d_post (perm o post), the L-level ops by the etree postorder alone.
+static hipError_t sweep_enqueue(Numeric& N, int family, int32_t op) {
+    const SweepFamily& K = SWEEP[family];
+    const SolvePlan& P = family ? N.SPM : N.SP;
+    double* io = family ? N.d_mbuf : N.d_sbuf;
+    const size_t wide = (family ? SOLVE_RHS : 1) * sizeof(double);
+    const int64_t n = N.S->n;
     hipStream_t s0 = N.stream;
+    const int32_t* post = op == SC_OP_SOLVE_A ? N.d_post : N.d_etpost;
+    auto zero_u = [&]() { return hipMemsetAsync(P.u, 0, (size_t)std::max<int64_t>(N.u_total, 1) * wide, s0); };
+    hipError_t e = hipSuccess;
+    switch (op) {
+        case SC_OP_SOLVE_A:
+        case SC_OP_SOLVE_L:
+        case SC_OP_SOLVE_LT: {
+            // L y = c bottom-up (c in place, y to P.y), L^T x = y top-down in place on c
+            const bool up = op != SC_OP_SOLVE_LT, down = op != SC_OP_SOLVE_L;
+            e = K.permute(P.c, io, post, n, false, s0);
+            if (up && e == hipSuccess) e = zero_u();
+            if (up && e == hipSuccess) e = sweep_up(N, P, K, K.fwd, s0);
+            if (up && down && e == hipSuccess)
+                e = hipMemcpyAsync(P.c, P.y, (size_t)n * wide, hipMemcpyDeviceToDevice, s0);
+            if (down && e == hipSuccess) e = sweep_blocks(N, P, K.gemv, K.diag, false, s0);
+            if (e == hipSuccess) e = K.permute(down ? P.c : P.y, io, post, n, true, s0);
+            break;
+        }
+        case SC_OP_MUL_L:  // panels only; bottom-up: z in y (read-only), x accumulated in c and u
+            e = family ? K.permute(P.y, io, post, n, false, s0) : hipErrorInvalidValue;
+            if (e == hipSuccess) e = hipMemsetAsync(P.c, 0, (size_t)n * wide, s0);
+            if (e == hipSuccess) e = zero_u();
+            if (e == hipSuccess) e = sweep_up(N, P, K, launch_mul_l_multi, s0);
+            if (e == hipSuccess) e = K.permute(P.c, io, post, n, true, s0);
+            break;
+        case SC_OP_MUL_LT:  // panels only; no front waits for another, the steps share the part buffer only
+            e = family ? K.permute(P.y, io, post, n, false, s0) : hipErrorInvalidValue;
+            if (e == hipSuccess) e = sweep_blocks(N, P, launch_mul_lt_gemv_multi, launch_mul_lt_diag_multi, true, s0);
+            if (e == hipSuccess) e = K.permute(P.c, io, post, n, true, s0);
+            break;
+        default: {  // SC_OP_PERM, SC_OP_PERM_T
+            const bool fwd = op == SC_OP_PERM;
+            e = K.permute(P.c, io, fwd ? N.d_post : post, n, false, s0);
+            if (e == hipSuccess) e = K.permute(P.c, io, fwd ? post : N.d_post, n, true, s0);
+        }
+    }
+    return e;
+}
+
+// Runs op on the family's io: eagerly (sc_debug_solve_eager), or as the op's graph,
+// captured at its first use (a single-stream chain: ~700 dependent steps per sweep at
+// 128^3 replayed as one hipGraph) after the inverses a solve needs are in place.
+static int64_t apply_run(Numeric& N, int family, int32_t op) {
+    hipStream_t s0 = N.stream;
+    if (op == SC_OP_SOLVE_A || op == SC_OP_SOLVE_L || op == SC_OP_SOLVE_LT) TRY(solve_inverses(N));
     if (N.solve_eager) {
-        HIP_TRY(sweeps());
+        HIP_TRY(sweep_enqueue(N, family, op));
         return SC_OK;
     }
     hipGraphExec_t& gexec = N.apply_gexec[family][op];
     if (!gexec) {
         HIP_TRY(hipStreamBeginCapture(s0, hipStreamCaptureModeThreadLocal));
-        hipError_t e = sweeps();
+        hipError_t e = sweep_enqueue(N, family, op);
         hipGraph_t g = nullptr;
         hipError_t e2 = hipStreamEndCapture(s0, &g);
         HIP_TRY(e);
@@ -437,84 +396,16 @@ static int64_t apply_run(Numeric& N, int family, int32_t op, F&& sweeps) {
     return SC_OK;
 }
 
-static bool apply_needs_inverses(int32_t op) { return op == SC_OP_SOLVE_L || op == SC_OP_SOLVE_LT; }
-
-int64_t solve_inverses(Numeric& N) {
-    if (N.inv_gen != N.factor_gen) {  // shared with the solves
-        HIP_TRY(launch_solve_inv(N.SP, N.d_sinv, N.n_sinv, N.d_sinv2, N.n_sinv2, N.stream));
-        N.inv_gen = N.factor_gen;
-    }
-    return SC_OK;
-}
-
-// in / out: the copy kinds of the caller's B and X (device or host memory)
+// The graphs work on the handle's own io, so each is captured once, whatever buffers the
+// caller passes.  in / out: the copy kinds of the caller's B and X (device or host memory)
 static int64_t apply_multi(Numeric& N, int32_t op, int32_t nrhs, const double* B, int64_t ldb, double* X, int64_t ldx,
                            hipMemcpyKind in, hipMemcpyKind out) {
-    if (op == SC_OP_SOLVE_A) return solve_multi(N, nrhs, B, ldb, X, ldx, in, out);
-    if (!N.factored) return SC_ERR_STATE;
-    const int64_t st = numeric_status(N);
-    if (st != SC_OK) return st;
-    TRY(apply_prepare(N));
+    TRY(solve_begin(N, op != SC_OP_SOLVE_A));
     const int64_t n = N.S->n;
     if (n == 0 || nrhs == 0) return SC_OK;
     if (!N.multi_ready) TRY(solve_multi_build(N));
     hipStream_t s0 = N.stream;
-    const SolvePlan& P = N.SPM;
-    double* io = N.d_mbuf;  // the handle's own panel, as in solve_multi
-    const size_t wide = (size_t)SOLVE_RHS * sizeof(double);
-    const int32_t* post = N.d_etpost;
-    auto zero_u = [&]() { return hipMemsetAsync(P.u, 0, (size_t)std::max<int64_t>(N.u_total, 1) * wide, s0); };
-    auto sweeps = [&]() -> hipError_t {
-        hipError_t e = hipSuccess;
-        switch (op) {
-            case SC_OP_SOLVE_L:  // the solve's forward half: y = L^-1 c
-                e = launch_permute_multi(P.c, io, post, n, false, s0);
-                if (e == hipSuccess) e = zero_u();
-                for (size_t i = 0; e == hipSuccess && i < N.solve_steps.size(); ++i) {
-                    const Numeric::SolveStep& t = N.solve_steps[i];
-                    e = launch_solve_fwd_gather_multi(P, N.d_sgather + t.gaoff, t.gacount, s0);
-                    if (e == hipSuccess) e = launch_solve_fwd_multi(P, N.d_sfwd + t.foff, t.fcount, s0);
-                }
-                if (e == hipSuccess) e = launch_permute_multi(P.y, io, post, n, true, s0);
-                break;
-            case SC_OP_SOLVE_LT:  // its backward half, in place on c
-                e = launch_permute_multi(P.c, io, post, n, false, s0);
-                for (size_t i = N.solve_steps.size(); e == hipSuccess && i-- > 0;) {
-                    const Numeric::SolveStep& t = N.solve_steps[i];
-                    e = launch_solve_gemv_multi(P, N.d_sgemv + t.goff, t.gcount, s0);
-                    if (e == hipSuccess) e = launch_solve_diag_multi(P, N.d_sdiag + t.doff, t.dcount, s0);
-                }
-                if (e == hipSuccess) e = launch_permute_multi(P.c, io, post, n, true, s0);
-                break;
-            case SC_OP_MUL_L:  // bottom-up: z in y (read-only), x accumulated in c and u
-                e = launch_permute_multi(P.y, io, post, n, false, s0);
-                if (e == hipSuccess) e = hipMemsetAsync(P.c, 0, (size_t)n * wide, s0);
-                if (e == hipSuccess) e = zero_u();
-                for (size_t i = 0; e == hipSuccess && i < N.solve_steps.size(); ++i) {
-                    const Numeric::SolveStep& t = N.solve_steps[i];
-                    e = launch_solve_fwd_gather_multi(P, N.d_sgather + t.gaoff, t.gacount, s0);
-                    if (e == hipSuccess) e = launch_mul_l_multi(P, N.d_sfwd + t.foff, t.fcount, s0);
-                }
-                if (e == hipSuccess) e = launch_permute_multi(P.c, io, post, n, true, s0);
-                break;
-            case SC_OP_MUL_LT:  // no front waits for another; the steps share the part buffer only
-                e = launch_permute_multi(P.y, io, post, n, false, s0);
-                for (size_t i = 0; e == hipSuccess && i < N.solve_steps.size(); ++i) {
-                    const Numeric::SolveStep& t = N.solve_steps[i];
-                    e = launch_mul_lt_gemv_multi(P, N.d_sgemv + t.goff, t.gcount, s0);
-                    if (e == hipSuccess) e = launch_mul_lt_diag_multi(P, N.d_sdiag + t.doff, t.dcount, s0);
-                }
-                if (e == hipSuccess) e = launch_permute_multi(P.c, io, post, n, true, s0);
-                break;
-            default: {  // SC_OP_PERM, SC_OP_PERM_T
-                const bool fwd = op == SC_OP_PERM;
-                e = launch_permute_multi(P.c, io, fwd ? N.d_post : post, n, false, s0);
-                if (e == hipSuccess) e = launch_permute_multi(P.c, io, fwd ? post : N.d_post, n, true, s0);
-            }
-        }
-        return e;
-    };
-    if (apply_needs_inverses(op)) TRY(solve_inverses(N));
+    double* io = N.d_mbuf;
     const size_t colb = (size_t)n * sizeof(double);
     for (int32_t j0 = 0; j0 < nrhs; j0 += SOLVE_RHS) {
         const int nr = std::min<int32_t>(SOLVE_RHS, nrhs - j0);
@@ -522,7 +413,7 @@ static int64_t apply_multi(Numeric& N, int32_t op, int32_t nrhs, const double* B
                                  s0));
         // a partial panel: true zero columns, never the caller's memory
         if (nr < SOLVE_RHS) HIP_TRY(hipMemsetAsync(io + (int64_t)nr * n, 0, (size_t)(SOLVE_RHS - nr) * colb, s0));
-        TRY(apply_run(N, 1, op, sweeps));
+        TRY(apply_run(N, 1, op));
         HIP_TRY(hipMemcpy2DAsync(X + (int64_t)j0 * ldx, (size_t)ldx * sizeof(double), io, colb, colb, (size_t)nr, out,
                                  s0));
         // host memory: one panel staged at a time
@@ -543,67 +434,25 @@ int64_t numeric_apply_host_multi(Numeric& N, int32_t op, int32_t nrhs, const dou
 }
 
 int64_t numeric_apply_device(Numeric& N, int32_t op, const double* d_b, double* d_x) {
-    if (op == SC_OP_SOLVE_A) return numeric_solve_device(N, d_b, d_x);
     const int64_t n = N.S->n;
     // the products have panel kernels only: a panel of one column
     if (op == SC_OP_MUL_L || op == SC_OP_MUL_LT) return numeric_apply_device_multi(N, op, 1, d_b, n, d_x, n);
-    if (!N.factored) return SC_ERR_STATE;
-    const int64_t st = numeric_status(N);
-    if (st != SC_OK) return st;
-    TRY(apply_prepare(N));
+    TRY(solve_begin(N, op != SC_OP_SOLVE_A));
     if (n == 0) return SC_OK;
     hipStream_t s0 = N.stream;
-    double* io = N.d_sbuf;  // the handle's own vector, as in numeric_solve_device
-    const int32_t* post = N.d_etpost;
-    auto sweeps = [&]() -> hipError_t {
-        hipError_t e = hipSuccess;
-        switch (op) {
-            case SC_OP_SOLVE_L:
-                e = launch_permute(N.SP.c, io, post, n, false, s0);
-                if (e == hipSuccess)
-                    e = hipMemsetAsync(N.SP.u, 0, (size_t)std::max<int64_t>(N.u_total, 1) * sizeof(double), s0);
-                for (size_t i = 0; e == hipSuccess && i < N.solve_steps.size(); ++i) {
-                    const Numeric::SolveStep& t = N.solve_steps[i];
-                    e = launch_solve_fwd_gather(N.SP, N.d_sgather + t.gaoff, t.gacount, s0);
-                    if (e == hipSuccess) e = launch_solve_fwd(N.SP, N.d_sfwd + t.foff, t.fcount, s0);
-                }
-                if (e == hipSuccess) e = launch_permute(io, N.SP.y, post, n, true, s0);
-                break;
-            case SC_OP_SOLVE_LT:
-                e = launch_permute(N.SP.c, io, post, n, false, s0);
-                for (size_t i = N.solve_steps.size(); e == hipSuccess && i-- > 0;) {
-                    const Numeric::SolveStep& t = N.solve_steps[i];
-                    e = launch_solve_gemv(N.SP, N.d_sgemv + t.goff, t.gcount, s0);
-                    if (e == hipSuccess) e = launch_solve_diag(N.SP, N.d_sdiag + t.doff, t.dcount, s0);
-                }
-                if (e == hipSuccess) e = launch_permute(io, N.SP.c, post, n, true, s0);
-                break;
-            default: {  // SC_OP_PERM, SC_OP_PERM_T
-                const bool fwd = op == SC_OP_PERM;
-                e = launch_permute(N.SP.c, io, fwd ? N.d_post : post, n, false, s0);
-                if (e == hipSuccess) e = launch_permute(io, N.SP.c, fwd ? post : N.d_post, n, true, s0);
-            }
-        }
-        return e;
-    };
-    if (apply_needs_inverses(op)) TRY(solve_inverses(N));
+    double* io = N.d_sbuf;
     const size_t nb = (size_t)n * sizeof(double);
     if (d_b != io) HIP_TRY(hipMemcpyAsync(io, d_b, nb, hipMemcpyDeviceToDevice, s0));
-    TRY(apply_run(N, 0, op, sweeps));
+    TRY(apply_run(N, 0, op));
     if (d_x != io) HIP_TRY(hipMemcpyAsync(d_x, io, nb, hipMemcpyDeviceToDevice, s0));
     HIP_TRY(hipStreamSynchronize(s0));
     return SC_OK;
 }
 
 int64_t numeric_apply_host(Numeric& N, int32_t op, const double* b, double* x) {
-    if (op == SC_OP_SOLVE_A) return numeric_solve_host(N, b, x);
     const int64_t n = N.S->n;
     if (op == SC_OP_MUL_L || op == SC_OP_MUL_LT) return numeric_apply_host_multi(N, op, 1, b, n, x, n);
-    if (!N.factored) return SC_ERR_STATE;
-    const int64_t st = numeric_status(N);
-    if (st != SC_OK) return st;
-    HIP_TRY(hipSetDevice(N.device));
-    if (!N.solve_ready) TRY(solve_build(N));
+    TRY(solve_begin(N, op != SC_OP_SOLVE_A));  // d_sbuf is the plan's
     const size_t nb = (size_t)n * sizeof(double);
     if (nb == 0) return SC_OK;
     HIP_TRY(hipMemcpy(N.d_sbuf, b, nb, hipMemcpyHostToDevice));
@@ -612,11 +461,26 @@ int64_t numeric_apply_host(Numeric& N, int32_t op, const double* b, double* x) {
     return SC_OK;
 }
 
+// The solves are the operator SC_OP_SOLVE_A.
+int64_t numeric_solve_device(Numeric& N, const double* d_b, double* d_x) {
+    return numeric_apply_device(N, SC_OP_SOLVE_A, d_b, d_x);
+}
+
+int64_t numeric_solve_host(Numeric& N, const double* b, double* x) {
+    return numeric_apply_host(N, SC_OP_SOLVE_A, b, x);
+}
+
+int64_t numeric_solve_device_multi(Numeric& N, int32_t nrhs, const double* d_B, int64_t ldb, double* d_X,
+                                   int64_t ldx) {
+    return numeric_apply_device_multi(N, SC_OP_SOLVE_A, nrhs, d_B, ldb, d_X, ldx);
+}
+
+int64_t numeric_solve_host_multi(Numeric& N, int32_t nrhs, const double* B, int64_t ldb, double* X, int64_t ldx) {
+    return numeric_apply_host_multi(N, SC_OP_SOLVE_A, nrhs, B, ldb, X, ldx);
+}
+
 int64_t numeric_logdet(Numeric& N, double* logdet) {
-    if (!N.factored) return SC_ERR_STATE;
-    const int64_t st = numeric_status(N);
-    if (st != SC_OK) return st;
-    TRY(solve_prepare(N));
+    TRY(solve_begin(N, false));
     const int64_t n = N.S->n;
     if (n == 0) {
         *logdet = 0.0;  // the empty product

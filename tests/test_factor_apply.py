@@ -195,24 +195,29 @@ def test_products_do_not_see_the_stored_inverses(gpu, name, kw):
 def test_ops_bitwise_repeatable_lap20(gpu):
     A = _matrix("lap20")
     Z = _rhs("lap20", 16, seed=19)
-    runs = {op: [] for op in L_OPS}
+    # the plain solves run between the operators on the same handle: every op and family
+    # replays a captured sweep of its own
+    calls = {OP_NAME[op]: (lambda num, op=op: num.apply(Z, op)) for op in L_OPS}
+    calls["solve(b)"] = lambda num: num.solve(Z[:, 0].copy())
+    calls["solve(B)"] = lambda num: num.solve(Z)
+    runs = {name: [] for name in calls}
     for rep in range(2):
         num = sc.Numeric(sc.Symbolic(A))
         assert num.factor(A.x) == 0
-        for op in L_OPS:
-            runs[op].append(num.apply(Z, op))
-            runs[op].append(num.apply(Z, op))
+        for name, call in calls.items():
+            runs[name].append(call(num))
+            runs[name].append(call(num))
         assert num.factor(A.x) == 0
-        for op in L_OPS:
-            runs[op].append(num.apply(Z, op))
+        for name, call in calls.items():
+            runs[name].append(call(num))
         if rep == 1:
             assert sc.lib().sc_debug_solve_eager(num.h, 1) == 0
-            for op in L_OPS:
-                runs[op].append(num.apply(Z, op))
-    for op in L_OPS:
-        assert len(runs[op]) == 7
-        for x in runs[op][1:]:
-            assert np.array_equal(runs[op][0], x), OP_NAME[op]
+            for name, call in calls.items():
+                runs[name].append(call(num))
+    for name in calls:
+        assert len(runs[name]) == 7
+        for x in runs[name][1:]:
+            assert np.array_equal(runs[name][0], x), name
 
 
 @pytest.mark.parametrize("name", ["lap20", "1138_bus"])
