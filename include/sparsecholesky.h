@@ -34,7 +34,7 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define SC_VERSION 121 /* still 1.2.1, additive: products with A, residuals and iterative refinement sc_spmv_structure / sc_spmv_*_multi / sc_residual_*_multi / sc_solve_refine_*_multi / sc_default_refine_options; still 1.2.1, additive: Schur complement sc_analyze_schur / sc_symbolic_schur / sc_schur_factor_* / sc_schur_matrix_* / sc_schur_condense_*_multi / sc_schur_expand_*_multi; still 1.2.1, additive: rank-k update / downdate sc_updown_check / sc_updown_host; still 1.2.1, additive: selected inversion sc_selinv / sc_selinv_diag_host / sc_selinv_diag_device / sc_selinv_export / sc_selinv_flops; still 1.2.1, additive: the factor operators sc_apply_host / sc_apply_device / sc_apply_host_multi / sc_apply_device_multi (enum sc_factor_op) and sc_logdet; still 1.2.1, additive: sc_solve_host_multi / sc_solve_device_multi (nrhs right-hand sides); 1.2.1:small merged fronts amalgamated past relax_wmax (different supernode partition of some inputs, same L); 1.2.0: persistent slab chain options removed; panel_prefactor, dist_local_pieces and SC_ORDER_AMD added; out-of-range lookahead / inner_order / ordering rejected */
+#define SC_VERSION 121 /* still 1.2.1, additive: conjugate gradients preconditioned with the factor sc_solve_pcg_*_multi / sc_default_pcg_options; still 1.2.1, additive: products with A, residuals and iterative refinement sc_spmv_structure / sc_spmv_*_multi / sc_residual_*_multi / sc_solve_refine_*_multi / sc_default_refine_options; still 1.2.1, additive: Schur complement sc_analyze_schur / sc_symbolic_schur / sc_schur_factor_* / sc_schur_matrix_* / sc_schur_condense_*_multi / sc_schur_expand_*_multi; still 1.2.1, additive: rank-k update / downdate sc_updown_check / sc_updown_host; still 1.2.1, additive: selected inversion sc_selinv / sc_selinv_diag_host / sc_selinv_diag_device / sc_selinv_export / sc_selinv_flops; still 1.2.1, additive: the factor operators sc_apply_host / sc_apply_device / sc_apply_host_multi / sc_apply_device_multi (enum sc_factor_op) and sc_logdet; still 1.2.1, additive: sc_solve_host_multi / sc_solve_device_multi (nrhs right-hand sides); 1.2.1:small merged fronts amalgamated past relax_wmax (different supernode partition of some inputs, same L); 1.2.0: persistent slab chain options removed; panel_prefactor, dist_local_pieces and SC_ORDER_AMD added; out-of-range lookahead / inner_order / ordering rejected */
 
 enum sc_status {
     SC_OK = 0,
@@ -595,6 +595,72 @@ int64_t sc_solve_refine_host_multi(sc_numeric* num, const sc_refine_options* opt
                                    const double* B, int64_t ldb, double* X, int64_t ldx, sc_refine_info* info);
 int64_t sc_solve_refine_device_multi(sc_numeric* num, const sc_refine_options* opt, int32_t nrhs, const double* d_Ax,
                                      const double* d_B, int64_t ldb, double* d_X, int64_t ldx, sc_refine_info* info);
+
+/* Conjugate gradients on the GPU with the factor as the preconditioner: X = A'^-1 B for the
+ * values A' the caller passes, which need not be the factored ones -- a Newton or interior-
+ * point step, a time step with drifted coefficients, Q(theta) under an optimiser, a
+ * modification sc_updown_host rejects.  Where sc_solve_refine_*_multi contracts the error by
+ * rho(I - inv(A) A') per step and cannot work once an eigenvalue of inv(A) A' reaches 2, CG
+ * needs A' symmetric positive definite and nothing else: k eigenvalues of inv(A) A' away from
+ * 1 cost k + 1 steps in exact arithmetic (A' = 3 A: one step), the rest sqrt(cond(inv(A) A'))
+ * per digit.  Arrays, numbering, leading dimensions and the values Ax / d_Ax (NULL: the copy
+ * sc_factor made) follow the rules of the refinement entry points above.
+ * Per column, with M the factor's solve (sc_solve_*_multi) and 2-norms:
+ *   x_0 = M b, sc_solve_*_multi's result bit for bit (use_x0 = 0), or X as the caller left it
+ *         (use_x0 = 1: a warm start; the host form then reads X);
+ *   r = b - A' x_0 (one fma per entry, as SC_RESIDUAL_FP64);
+ *   CONVERGED with iters = 0 when |r| <= tol |b| (an all-zero b: x = 0, CONVERGED);
+ *   MAXITER   with iters = 0 when max_iter = 0;
+ *   z = M r; rho = r.z; p = z;
+ *   repeat: q = A' p; pq = p.q;
+ *     BREAKDOWN  pq <= 0 or not finite: x stays at the last iterate
+ *     alpha = rho / pq; x += alpha p; r -= alpha q; iters += 1;
+ *     CONVERGED  |r| <= tol |b|
+ *     MAXITER    iters == max_iter
+ *     z = M r; rho' = r.z;
+ *     BREAKDOWN  rho' <= 0 or not finite (the same test guards the first rho)
+ *     p = z + (rho' / rho) p.
+ * BREAKDOWN is how values that are not positive definite show: p.A'p <= 0 for some direction
+ * (A' = -A breaks down at once with x = x_0).  An indefinite A' may also run to MAXITER; it is
+ * never reported CONVERGED unless the residual it returns is that small.  tol = 0 is legal and
+ * runs to max_iter or breakdown.  With the factored values and the default tol the first
+ * test holds and the call returns the panel solve bit for bit with iters = 0.
+ * Every sum is an fma chain in an order fixed by n alone, alpha, beta and the decisions are
+ * taken on the host per column, and a column that has stopped is not written again: a
+ * column's result does not depend on the columns it travels with or on its position, and is
+ * bitwise repeatable across calls and handles.  No atomics.
+ * sc_pcg_info (nrhs entries, host memory, may be NULL) describes the returned X: iters, state,
+ * relres = |r| / |b| of the recurrence's r (0 / 0 = 0), and from one more residual pass over
+ * the returned X relres_true = |b - A' x| / |b| and the two backward errors of
+ * sc_residual_*_multi (SC_RESIDUAL_FP64).
+ * Status: as sc_solve_refine_*_multi -- SC_ERR_STATE before a factorization; a failed
+ * factorization returns its status > 0 and writes nothing; nrhs == 0 or n == 0: SC_OK; multi-
+ * rank and emulated handles SC_ERR_NOTIMPL with a message.  SC_ERR_ARG with the entry point's
+ * name in sc_last_error for a null handle or array, a leading dimension below n, nrhs < 0, an
+ * options struct of the wrong struct_size, max_iter < 0, tol outside [0, 1), use_x0 other than
+ * 0 or 1, and X == B.  Calls are synchronous on the handle's stream.
+ * Device memory, counted in sc_numeric_memory info[0], allocated at the first call and kept
+ * until sc_free_numeric, besides what the refinement section lists (allocated by whichever
+ * call comes first) and what the first sc_solve_*_multi allocates:
+ *   3 x 128 n                    the z, p and q panels (n at least 1)
+ *   256 per 1024 rows (rounded up, at least one)    partial sums
+ *   512                          the sums of a step */
+enum { SC_PCG_CONVERGED = 0, SC_PCG_MAXITER = 1, SC_PCG_BREAKDOWN = 2 };
+typedef struct sc_pcg_options {
+    int32_t struct_size; /* sizeof(sc_pcg_options), set by sc_default_pcg_options */
+    int32_t max_iter;    /* steps at most (100) */
+    int32_t use_x0;      /* 0: start from the panel solve; 1: from X as passed */
+    double tol;          /* 1e-10; stop at |r|_2 <= tol |b|_2 */
+} sc_pcg_options;
+typedef struct sc_pcg_info {
+    int32_t iters, state;
+    double relres, relres_true, berr_norm, berr_comp;
+} sc_pcg_info;
+void sc_default_pcg_options(sc_pcg_options* opt);
+int64_t sc_solve_pcg_host_multi(sc_numeric* num, const sc_pcg_options* opt, int32_t nrhs, const double* Ax,
+                                const double* B, int64_t ldb, double* X, int64_t ldx, sc_pcg_info* info);
+int64_t sc_solve_pcg_device_multi(sc_numeric* num, const sc_pcg_options* opt, int32_t nrhs, const double* d_Ax,
+                                  const double* d_B, int64_t ldb, double* d_X, int64_t ldx, sc_pcg_info* info);
 
 /* ---------------- reference-API helpers (host) ----------------
  * Each mirrors one reference function, with int64 column pointers. */

@@ -109,6 +109,25 @@ int64_t sc_debug_schur_llt(const double* dD, int32_t ns, int64_t ldd, double* dS
 int64_t sc_debug_spmv(int32_t mode, int32_t n, const int64_t* rp, const int32_t* ci, const int64_t* sp, int64_t nval,
                       const double* d_Ax, int32_t nrhs, const double* d_X, int64_t ldx, const double* d_B, int64_t ldb,
                       double* d_R, int64_t ldr, double* d_W, int64_t ldw, double* d_norms);
+/* One vector kernel of the conjugate gradients alone (no handle) on caller panels in device
+ * memory, n x nrhs column-major, nrhs <= 16, leading dimensions >= n; mask: bit c set = column
+ * c takes part (bits >= nrhs are ignored); coef: 16 host doubles, one per column; out: 2 x 16
+ * host doubles, value q of column c at 16 q + c, zero for a column outside the mask.
+ *   which 0  dot:     out[c] = sum_i A(i, c) B(i, c) and, with d_C, out[16 + c] = sum_i A(i, c)
+ *                     C(i, c) (d_C may be NULL, coef unused);
+ *   which 1  update:  A += coef_c C, B -= coef_c D, each entry one fma; out[c] = sum_i B(i, c)^2
+ *                     of the new B (the iteration's x, r, p, q);
+ *   which 2  direction: A = C + coef_c A (one fma; the iteration's p and z); d_T (may be NULL):
+ *                     n x 16 doubles, the new A in 16-wide row-major form, d_T[16 i + c], zero
+ *                     in the columns outside the mask and those >= nrhs (out unused);
+ *   which 3  the same with A = C: A is not read, coef unused.
+ * Rows >= n, columns >= nrhs and columns outside the mask are neither read nor written.  The
+ * sums are bitwise repeatable.  Everything is validated before a launch: an unknown kernel, n
+ * < 0, nrhs outside [0, 16], a null array the kernel needs or a leading dimension below n
+ * return SC_ERR_ARG with a message; n == 0 or nrhs == 0: SC_OK, out zero.  Synchronous. */
+int64_t sc_debug_pcg_vec(int32_t which, int32_t n, int32_t nrhs, uint32_t mask, const double* coef, double* d_A,
+                         int64_t lda, double* d_B, int64_t ldb, const double* d_C, int64_t ldc, const double* d_D,
+                         int64_t ldd, double* d_T, double* out);
 /* Chain launches (runs of single small-front levels): enable = 1 makes the next
  * eager factorizations record 8 shader-clock stamps per chained front (phase
  * boundaries); enable = 0 copies up to cap of them to out.  Returns the count. */

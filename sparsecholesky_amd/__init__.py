@@ -48,6 +48,7 @@ __all__ = [
     "SC_OP_SOLVE_A", "SC_OP_SOLVE_L", "SC_OP_SOLVE_LT", "SC_OP_MUL_L", "SC_OP_MUL_LT", "SC_OP_PERM", "SC_OP_PERM_T",
     "RefineOptions", "RefineInfo", "SC_RESIDUAL_FP64", "SC_RESIDUAL_DD",
     "SC_REFINE_CONVERGED", "SC_REFINE_STALLED", "SC_REFINE_MAXITER", "SC_REFINE_DIVERGED",
+    "PcgOptions", "PcgInfo", "SC_PCG_CONVERGED", "SC_PCG_MAXITER", "SC_PCG_BREAKDOWN",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -59,6 +60,8 @@ SC_OP_SOLVE_A, SC_OP_SOLVE_L, SC_OP_SOLVE_LT, SC_OP_MUL_L, SC_OP_MUL_LT, SC_OP_P
 # residual accumulation of Numeric.residual / solve_refined, and the states a refined column ends in
 SC_RESIDUAL_FP64, SC_RESIDUAL_DD = 0, 1
 SC_REFINE_CONVERGED, SC_REFINE_STALLED, SC_REFINE_MAXITER, SC_REFINE_DIVERGED = range(4)
+# the states a column of Numeric.solve_pcg ends in
+SC_PCG_CONVERGED, SC_PCG_MAXITER, SC_PCG_BREAKDOWN = range(3)
 _RESIDUAL_MODES = {"fp64": SC_RESIDUAL_FP64, "dd": SC_RESIDUAL_DD}
 _STATUS = {
     -1: "invalid argument", -2: "host allocation failed", -3: "HIP runtime error",
@@ -95,6 +98,15 @@ class RefineOptions(C.Structure):
 class RefineInfo(C.Structure):
     _fields_ = [("iters", C.c_int32), ("state", C.c_int32), ("berr_norm", C.c_double),
                 ("berr_comp", C.c_double), ("dx_ratio", C.c_double)]
+
+
+class PcgOptions(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("max_iter", C.c_int32), ("use_x0", C.c_int32), ("tol", C.c_double)]
+
+
+class PcgInfo(C.Structure):
+    _fields_ = [("iters", C.c_int32), ("state", C.c_int32), ("relres", C.c_double), ("relres_true", C.c_double),
+                ("berr_norm", C.c_double), ("berr_comp", C.c_double)]
 
 
 class SymbolicStats(C.Structure):
@@ -179,6 +191,9 @@ _SIGS = [
     ("sc_residual_device_multi", _I64, [_P, _I32, _I32, _P, _P, _I64, _P, _I64, _P, _I64, _P, _P]),
     ("sc_solve_refine_host_multi", _I64, [_P, C.POINTER(RefineOptions), _I32, _P, _P, _I64, _P, _I64, _P]),
     ("sc_solve_refine_device_multi", _I64, [_P, C.POINTER(RefineOptions), _I32, _P, _P, _I64, _P, _I64, _P]),
+    ("sc_default_pcg_options", None, [C.POINTER(PcgOptions)]),
+    ("sc_solve_pcg_host_multi", _I64, [_P, C.POINTER(PcgOptions), _I32, _P, _P, _I64, _P, _I64, _P]),
+    ("sc_solve_pcg_device_multi", _I64, [_P, C.POINTER(PcgOptions), _I32, _P, _P, _I64, _P, _I64, _P]),
     ("sc_etree", _I64, [_I64, _P, _P, _P]),
     ("sc_post_order", _I64, [_I64, _P, _P]),
     ("sc_col_count", _I64, [_I64, _P, _P, _P, _P, _P]),
@@ -209,6 +224,7 @@ _SIGS = [
     ("sc_debug_solve_step", _I64, [_P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P]),
     ("sc_debug_solve_gather", _I64, [_I32, _I32, _I32, _I32, _P, _P, _P, _P, _P]),
     ("sc_debug_spmv", _I64, [_I32, _I32, _P, _P, _P, _I64, _P, _I32, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _P]),
+    ("sc_debug_pcg_vec", _I64, [_I32, _I32, _I32, C.c_uint32, _P, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _P]),
     ("sc_debug_bench", _I64, [_I32, _I32, _I32, _I32, _I32, C.POINTER(_D)]),
     ("sc_device_count", _I64, []),
     ("sc_debug_chain_stamps", _I64, [_P, _I32, _P, _I64]),
@@ -1143,6 +1159,57 @@ class Numeric:
         if st > 0:
             raise LibraryError(f"solve_refined_device_multi: A is not positive definite (column {st})")
         return self._refine_info(info, nrhs, False)
+
+    @staticmethod
+    def _pcg_options(tol: float, max_iter: int, use_x0: bool) -> PcgOptions:
+        o = PcgOptions()
+        lib().sc_default_pcg_options(C.byref(o))
+        o.tol, o.max_iter, o.use_x0 = tol, max_iter, int(use_x0)
+        return o
+
+    @staticmethod
+    def _pcg_info(info, k: int, one: bool) -> dict:
+        d = {f: np.array([getattr(info[j], f) for j in range(k)]) for f, _ in PcgInfo._fields_}
+        return {f: v[0].item() for f, v in d.items()} if one else d
+
+    def solve_pcg(self, B: np.ndarray, Ax=None, tol: float = 1e-10, max_iter: int = 100, x0=None) -> tuple:
+        """(X, info): X = A'^-1 B by conjugate gradients on the values ``Ax`` (``None``: those
+        of the last :meth:`factor`), preconditioned with the factor this handle holds, until
+        the 2-norm of the residual is at most ``tol`` times that of B's column.  ``x0``: a
+        starting array of B's shape (``None``: the panel solve of B).  ``info``: a dict of
+        arrays over the columns -- iters, state (SC_PCG_*), relres, relres_true, berr_norm,
+        berr_comp -- describing the returned X (scalars for 1-D input).  B (n,) or (n, k)
+        (sc_solve_pcg_host_multi)."""
+        Bf, one = self._panel_in(B, "solve_pcg")
+        n, k = Bf.shape
+        if x0 is None:
+            X = np.zeros((n, k), dtype=np.float64, order="F")
+        else:
+            X0, _ = self._panel_in(x0, "solve_pcg")
+            if X0.shape != Bf.shape:
+                raise ValueError(f"solve_pcg: B is {Bf.shape}, x0 {X0.shape}")
+            X = np.array(X0, dtype=np.float64, order="F", copy=True)
+        info = (PcgInfo * max(k, 1))()
+        o = self._pcg_options(tol, max_iter, x0 is not None)
+        ld = max(n, 1)
+        st = _check(lib().sc_solve_pcg_host_multi(self.h, C.byref(o), k, _ptr(self._values(Ax)), _ptr(Bf), ld,
+                                                  _ptr(X), ld, info), "solve_pcg")
+        if st > 0:
+            raise LibraryError(f"solve_pcg: A is not positive definite (column {st})")
+        return (X[:, 0] if one else X), self._pcg_info(info, k, one)
+
+    def solve_pcg_device_multi(self, d_Ax_ptr: int, d_B_ptr: int, nrhs: int, ldb: int, d_X_ptr: int, ldx: int,
+                               tol: float = 1e-10, max_iter: int = 100, use_x0: bool = False) -> dict:
+        """:meth:`solve_pcg` with device arrays (X must not be B; with ``use_x0`` X holds the
+        starting vectors); returns the info dict."""
+        info = (PcgInfo * max(nrhs, 1))()
+        o = self._pcg_options(tol, max_iter, use_x0)
+        st = _check(lib().sc_solve_pcg_device_multi(self.h, C.byref(o), nrhs, C.c_void_p(d_Ax_ptr or None),
+                                                    C.c_void_p(d_B_ptr), ldb, C.c_void_p(d_X_ptr), ldx, info),
+                    "solve_pcg_device_multi")
+        if st > 0:
+            raise LibraryError(f"solve_pcg_device_multi: A is not positive definite (column {st})")
+        return self._pcg_info(info, nrhs, False)
 
     def selinv(self) -> int:
         """Selected inversion: every entry of A^-1 on the pattern of L into the handle's Z

@@ -922,6 +922,64 @@ int64_t sc_solve_refine_device_multi(sc_numeric* num, const sc_refine_options* o
     return refine_multi(num, opt, nrhs, d_Ax, d_B, ldb, d_X, ldx, info, false, "sc_solve_refine_device_multi");
 }
 
+// ---- conjugate gradients preconditioned with the factor ----
+void sc_default_pcg_options(sc_pcg_options* opt) {
+    if (!opt) return;
+    std::memset(opt, 0, sizeof(*opt));
+    opt->struct_size = (int32_t)sizeof(sc_pcg_options);
+    opt->max_iter = 100;
+    opt->use_x0 = 0;
+    opt->tol = 1e-10;
+}
+
+static int64_t pcg_multi(sc_numeric* num, const sc_pcg_options* opt, int32_t nrhs, const double* Ax, const double* B,
+                         int64_t ldb, double* X, int64_t ldx, sc_pcg_info* info, bool host, const char* who) {
+    int64_t rc = panel_args(num, nrhs, {{B, ldb, "B"}, {X, ldx, "X"}}, who);
+    if (rc != SC_OK) return rc;
+    sc_pcg_options o;
+    sc_default_pcg_options(&o);
+    const char* bad = nullptr;
+    if (opt) {
+        if (opt->struct_size != (int32_t)sizeof(sc_pcg_options))
+            bad = "sc_pcg_options.struct_size does not match this library's sizeof(sc_pcg_options): initialise the "
+                  "options with sc_default_pcg_options()";
+        else
+            o = *opt;
+    }
+    if (!bad && o.max_iter < 0) bad = "max_iter < 0";
+    if (!bad && !(o.tol >= 0.0 && o.tol < 1.0)) bad = "tol outside [0, 1)";
+    if (!bad && o.use_x0 != 0 && o.use_x0 != 1) bad = "use_x0 is neither 0 nor 1";
+    if (!bad && nrhs > 0 && num->N->S->n > 0 && (const double*)X == B)
+        bad = "X aliases B (the iteration needs B after X exists)";
+    if (bad) {
+        g_last_error = std::string(who) + ": " + bad;
+        return SC_ERR_ARG;
+    }
+    try {
+        rc = sc::numeric_solve_pcg(*num->N, o, nrhs, Ax, B, ldb, X, ldx, info, host, who);
+    } catch (const std::bad_alloc&) {
+        return SC_ERR_NOMEM;
+    }
+    if (rc < 0) g_last_error = num->N->err;
+    return rc;
+}
+
+int64_t sc_solve_pcg_host_multi(sc_numeric* num, const sc_pcg_options* opt, int32_t nrhs, const double* Ax,
+                                const double* B, int64_t ldb, double* X, int64_t ldx, sc_pcg_info* info) {
+    return pcg_multi(num, opt, nrhs, Ax, B, ldb, X, ldx, info, true, "sc_solve_pcg_host_multi");
+}
+int64_t sc_solve_pcg_device_multi(sc_numeric* num, const sc_pcg_options* opt, int32_t nrhs, const double* d_Ax,
+                                  const double* d_B, int64_t ldb, double* d_X, int64_t ldx, sc_pcg_info* info) {
+    return pcg_multi(num, opt, nrhs, d_Ax, d_B, ldb, d_X, ldx, info, false, "sc_solve_pcg_device_multi");
+}
+
+int64_t sc_debug_pcg_vec(int32_t which, int32_t n, int32_t nrhs, uint32_t mask, const double* coef, double* d_A,
+                         int64_t lda, double* d_B, int64_t ldb, const double* d_C, int64_t ldc, const double* d_D,
+                         int64_t ldd, double* d_T, double* out) {
+    return sc::debug_pcg_vec(which, n, nrhs, mask, coef, d_A, lda, d_B, ldb, d_C, ldc, d_D, ldd, d_T, out,
+                             g_last_error);
+}
+
 int64_t sc_debug_spmv(int32_t mode, int32_t n, const int64_t* rp, const int32_t* ci, const int64_t* sp, int64_t nval,
                       const double* d_Ax, int32_t nrhs, const double* d_X, int64_t ldx, const double* d_B, int64_t ldb,
                       double* d_R, int64_t ldr, double* d_W, int64_t ldw, double* d_norms) {

@@ -1,10 +1,44 @@
 // Debug and microbenchmark hooks (sc_debug_syrk, sc_debug_syrk_ex, sc_debug_panel,
-// sc_debug_updown_block, sc_debug_solve_step, sc_debug_solve_gather, sc_debug_bench): the
-// SYRK, panel, update / downdate and solve / factor-product kernels on caller data, kernel
-// ceilings on synthetic operands.
+// sc_debug_updown_block, sc_debug_solve_step, sc_debug_solve_gather, sc_debug_pcg_vec,
+// sc_debug_bench): the SYRK, panel, update / downdate, solve / factor-product and conjugate-
+// gradient vector kernels on caller data, kernel ceilings on synthetic operands.
 #include "numeric_impl.hpp"
 
 namespace sc {
+
+int64_t debug_pcg_vec(int32_t which, int32_t n, int32_t nrhs, uint32_t mask, const double* coef, double* dA,
+                      int64_t lda, double* dB, int64_t ldb, const double* dC, int64_t ldc, const double* dD, int64_t ldd,
+                      double* dT, double* out, std::string& err) {
+    auto bad = [&](const char* what) {
+        err = std::string("sc_debug_pcg_vec: ") + what;
+        return (int64_t)SC_ERR_ARG;
+    };
+    if (which < 0 || which > 3) return bad("unknown kernel");
+    if (n < 0 || nrhs < 0 || nrhs > SOLVE_RHS) return bad("n < 0 or nrhs outside [0, 16]");
+    const bool sums = which <= 1, dir = which >= 2;
+    if ((sums && !out) || (which != 0 && which != 3 && !coef)) return bad("null array");
+    if (sums) std::fill(out, out + PCG_NQ * SOLVE_RHS, 0.0);
+    if (n == 0 || nrhs == 0) return SC_OK;
+    if (!dA || (!dir && !dB) || (which != 0 && !dC) || (which == 1 && !dD)) return bad("null array");
+    if (lda < n || (!dir && ldb < n) || (dC && ldc < n) || (which == 1 && ldd < n))
+        return bad("leading dimension below n");
+    PcgCoef k {};
+    if (coef) std::copy(coef, coef + SOLVE_RHS, k.v);
+    double* scratch = nullptr;
+    const size_t npart = (size_t)pcg_groups(n) * PCG_NQ * SOLVE_RHS, nout = PCG_NQ * SOLVE_RHS;
+    if (hipMalloc((void**)&scratch, (npart + nout) * sizeof(double)) != hipSuccess) return SC_ERR_DEVMEM;
+    hipError_t e;
+    if (which == 0)
+        e = launch_pcg_dot(dA, lda, dB, ldb, dC, ldc, n, nrhs, mask, scratch, scratch + npart, nullptr);
+    else if (which == 1)
+        e = launch_pcg_update(dA, lda, dB, ldb, dC, ldc, dD, ldd, n, nrhs, mask, k, scratch, scratch + npart, nullptr);
+    else
+        e = launch_pcg_dir(dA, lda, dC, ldc, n, nrhs, mask, k, which == 3, dT, nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess && sums) e = hipMemcpy(out, scratch + npart, nout * sizeof(double), hipMemcpyDeviceToHost);
+    (void)hipFree(scratch);
+    return e == hipSuccess ? SC_OK : SC_ERR_HIP;
+}
 
 int64_t debug_syrk_ex(double* dC, int ldc, const double* dA, int lda, int M, int Nn, int K, int bt, int lean, int tag,
                       int epi) {

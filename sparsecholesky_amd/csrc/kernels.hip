@@ -3956,4 +3956,183 @@ hipError_t launch_refine_add(double* X, int64_t ldx, const double* D, int64_t ld
     return hipGetLastError();
 }
 
+// ---- vector passes of the preconditioned conjugate gradients (kernels.hpp has the contracts) ----
+// Column c = blockIdx.y, rows [PCG_ROWS blockIdx.x, + PCG_ROWS): consecutive lanes read
+// consecutive rows of the column, so every load of a wave is one 512-byte run.
+
+// the workgroup's sums of s[0 .. NQ) to its partial slot: the wave by halving, the waves in order
+template <int NQ>
+__device__ __forceinline__ void pcg_block_sums(double (&s)[NQ], double* __restrict__ slot, int c) {
+    __shared__ double red[4][NQ];
+#pragma unroll
+    for (int q = 0; q < NQ; ++q)
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) s[q] += __shfl_down(s[q], o);
+    const int tid = threadIdx.x;
+    if ((tid & 63) == 0)
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) red[tid >> 6][q] = s[q];
+    __syncthreads();
+    if (tid < NQ) slot[tid * SOLVE_RHS + c] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+}
+
+template <bool TWO>
+__global__ __launch_bounds__(256) void pcg_dot_panel_kernel(const double* __restrict__ U, int64_t ldu,
+                                                            const double* __restrict__ V, int64_t ldv,
+                                                            const double* __restrict__ W, int64_t ldw, int64_t n,
+                                                            uint32_t mask, double* __restrict__ part) {
+    const int c = blockIdx.y;
+    if (!((mask >> c) & 1u)) return;
+    const int64_t i0 = (int64_t)blockIdx.x * PCG_ROWS + threadIdx.x;
+    const double* u = U + (int64_t)c * ldu;
+    const double* v = V + (int64_t)c * ldv;
+    const double* w = TWO ? W + (int64_t)c * ldw : nullptr;
+    double s[PCG_NQ] = {0.0, 0.0};
+#pragma unroll
+    for (int k = 0; k < PCG_ROWS / 256; ++k) {
+        const int64_t i = i0 + 256 * k;
+        if (i < n) {
+            const double ui = u[i];
+            s[0] = fma(ui, v[i], s[0]);
+            if (TWO) s[1] = fma(ui, w[i], s[1]);
+        }
+    }
+    pcg_block_sums<PCG_NQ>(s, part + (int64_t)blockIdx.x * (PCG_NQ * SOLVE_RHS), c);
+}
+
+__global__ __launch_bounds__(256) void pcg_update_kernel(double* __restrict__ X, int64_t ldx, double* __restrict__ R,
+                                                         int64_t ldr, const double* __restrict__ P, int64_t ldp,
+                                                         const double* __restrict__ Q, int64_t ldq, int64_t n,
+                                                         uint32_t mask, PcgCoef alpha, double* __restrict__ part) {
+    const int c = blockIdx.y;
+    if (!((mask >> c) & 1u)) return;
+    const int64_t i0 = (int64_t)blockIdx.x * PCG_ROWS + threadIdx.x;
+    const double a = alpha.v[c];
+    double* x = X + (int64_t)c * ldx;
+    double* r = R + (int64_t)c * ldr;
+    const double* p = P + (int64_t)c * ldp;
+    const double* q = Q + (int64_t)c * ldq;
+    double s[PCG_NQ] = {0.0, 0.0};
+#pragma unroll
+    for (int k = 0; k < PCG_ROWS / 256; ++k) {
+        const int64_t i = i0 + 256 * k;
+        if (i < n) {
+            x[i] = fma(a, p[i], x[i]);
+            const double ri = fma(-a, q[i], r[i]);
+            r[i] = ri;
+            s[0] = fma(ri, ri, s[0]);
+        }
+    }
+    pcg_block_sums<PCG_NQ>(s, part + (int64_t)blockIdx.x * (PCG_NQ * SOLVE_RHS), c);
+}
+
+// out[SOLVE_RHS q + c] = the partials of (q, c) added: slot s by lane group s % 16 in ascending
+// order, then the 16 group sums in order; zero for a column outside the mask
+__global__ __launch_bounds__(256) void pcg_final_kernel(const double* __restrict__ part, int64_t nslots, uint32_t mask,
+                                                        double* __restrict__ out) {
+    __shared__ double red[16][SOLVE_RHS];
+    const int tid = threadIdx.x, c = tid & 15, g = tid >> 4;
+    const bool on = (mask >> c) & 1u;
+    for (int q = 0; q < PCG_NQ; ++q) {
+        double v = 0.0;
+        if (on)
+            for (int64_t s = g; s < nslots; s += 16) v += part[(s * PCG_NQ + q) * SOLVE_RHS + c];
+        red[g][c] = v;
+        __syncthreads();
+        if (g == 0) {
+            for (int k = 1; k < 16; ++k) v += red[k][c];
+            out[SOLVE_RHS * q + c] = v;
+        }
+        __syncthreads();
+    }
+}
+
+// 64 rows per workgroup, all columns: the column-major side moves in runs of 64 rows, the
+// row-major copy leaves through LDS in runs of 16 columns (as spmv_transpose_kernel)
+template <bool FIRST, bool PT>
+__global__ __launch_bounds__(256) void pcg_dir_kernel(double* __restrict__ P, int64_t ldp,
+                                                      const double* __restrict__ Z, int64_t ldz, int64_t n,
+                                                      uint32_t mask, PcgCoef beta, double* __restrict__ pt) {
+    __shared__ double tile[64][SOLVE_RHS + 1];
+    const int tid = threadIdx.x, il = tid & 63, jq = tid >> 6;
+    const int64_t i0 = (int64_t)blockIdx.x * 64, i = i0 + il;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int c = jq + 4 * q;
+        double v = 0.0;
+        if (i < n && ((mask >> c) & 1u)) {
+            const double z = Z[i + (int64_t)c * ldz];
+            v = FIRST ? z : fma(beta.v[c], P[i + (int64_t)c * ldp], z);
+            P[i + (int64_t)c * ldp] = v;
+        }
+        if (PT) tile[il][c] = v;
+    }
+    if (PT) {
+        __syncthreads();
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int e = tid + 256 * q;
+            if (i0 + (e >> 4) < n) pt[i0 * SOLVE_RHS + e] = tile[e >> 4][e & 15];
+        }
+    }
+}
+
+static uint32_t pcg_mask(int nrhs, uint32_t mask) { return nrhs >= 32 ? mask : mask & ((1u << nrhs) - 1u); }
+
+static hipError_t pcg_finalize(int64_t n, uint32_t mask, double* part, double* out, hipStream_t st) {
+    hipLaunchKernelGGL(pcg_final_kernel, dim3(1), dim3(256), 0, st, part, n > 0 && mask ? pcg_groups(n) : (int64_t)0,
+                       mask, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_pcg_dot(const double* U, int64_t ldu, const double* V, int64_t ldv, const double* W, int64_t ldw,
+                          int64_t n, int nrhs, uint32_t mask, double* part, double* out, hipStream_t st) {
+    if (nrhs < 0 || nrhs > SOLVE_RHS || n < 0) return hipErrorInvalidValue;
+    mask = pcg_mask(nrhs, mask);
+    if (n > 0 && mask) {
+        const dim3 grid((unsigned)pcg_groups(n), nrhs);
+        if (W)
+            hipLaunchKernelGGL(pcg_dot_panel_kernel<true>, grid, dim3(256), 0, st, U, ldu, V, ldv, W, ldw, n, mask,
+                               part);
+        else
+            hipLaunchKernelGGL(pcg_dot_panel_kernel<false>, grid, dim3(256), 0, st, U, ldu, V, ldv, W, ldw, n, mask,
+                               part);
+    }
+    return pcg_finalize(n, mask, part, out, st);
+}
+
+hipError_t launch_pcg_update(double* X, int64_t ldx, double* R, int64_t ldr, const double* P, int64_t ldp,
+                             const double* Q, int64_t ldq, int64_t n, int nrhs, uint32_t mask, const PcgCoef& alpha,
+                             double* part, double* out, hipStream_t st) {
+    if (nrhs < 0 || nrhs > SOLVE_RHS || n < 0) return hipErrorInvalidValue;
+    mask = pcg_mask(nrhs, mask);
+    if (n > 0 && mask)
+        hipLaunchKernelGGL(pcg_update_kernel, dim3((unsigned)pcg_groups(n), nrhs), dim3(256), 0, st, X, ldx, R, ldr, P,
+                           ldp, Q, ldq, n, mask, alpha, part);
+    return pcg_finalize(n, mask, part, out, st);
+}
+
+hipError_t launch_pcg_dir(double* P, int64_t ldp, const double* Z, int64_t ldz, int64_t n, int nrhs, uint32_t mask,
+                          const PcgCoef& beta, bool first, double* pt, hipStream_t st) {
+    if (nrhs < 0 || nrhs > SOLVE_RHS || n < 0) return hipErrorInvalidValue;
+    mask = pcg_mask(nrhs, mask);
+    if (n == 0 || (!mask && !pt)) return hipSuccess;
+    const dim3 grid((unsigned)((n + 63) / 64));
+#define PCG_DIR(F, T) \
+    hipLaunchKernelGGL((pcg_dir_kernel<F, T>), grid, dim3(256), 0, st, P, ldp, Z, ldz, n, mask, beta, pt)
+    if (first) {
+        if (pt)
+            PCG_DIR(true, true);
+        else
+            PCG_DIR(true, false);
+    } else {
+        if (pt)
+            PCG_DIR(false, true);
+        else
+            PCG_DIR(false, false);
+    }
+#undef PCG_DIR
+    return hipGetLastError();
+}
+
 }  // namespace sc

@@ -357,6 +357,35 @@ hipError_t launch_refine_dnorm(const double* D, int64_t ldd, int64_t n, int nrhs
 hipError_t launch_refine_add(double* X, int64_t ldx, const double* D, int64_t ldd, int64_t n, int nrhs, uint32_t mask,
                              hipStream_t st);
 
+// ---- vector passes of the preconditioned conjugate gradients (pcg.cpp) ----
+// Panels are n x nrhs (<= SOLVE_RHS) column-major with a leading dimension; mask: bit c set =
+// column c takes part, a column whose bit is clear (and every column >= nrhs) is neither read
+// nor written.  The sums of a column run in one fixed tree that depends on n alone: a lane's
+// PCG_ROWS / 256 rows (stride 256) by fma, the 64 lanes of a wave by halving, the four waves
+// in order, one partial per workgroup of PCG_ROWS rows (part: PCG_NQ x SOLVE_RHS doubles per
+// workgroup, pcg_groups(n) of them), then one workgroup adds the partials: slot s to lane group
+// s % 16 in ascending order, the 16 group sums in order.  No atomics.
+constexpr int PCG_ROWS = 1024;  // rows per workgroup of the dot and update passes
+constexpr int PCG_NQ = 2;       // sums per column and pass
+struct PcgCoef {
+    double v[SOLVE_RHS];        // one coefficient per column, by value
+};
+inline int64_t pcg_groups(int64_t n) { return n > 0 ? (n + PCG_ROWS - 1) / PCG_ROWS : 1; }
+// out[c] = sum_i U(i, c) V(i, c) and, with W, out[SOLVE_RHS + c] = sum_i U(i, c) W(i, c); the
+// entries of out of a column outside the mask are set to zero (so is out's second row without W)
+hipError_t launch_pcg_dot(const double* U, int64_t ldu, const double* V, int64_t ldv, const double* W, int64_t ldw,
+                          int64_t n, int nrhs, uint32_t mask, double* part, double* out, hipStream_t st);
+// X(i, c) = fma(alpha_c, P(i, c), X(i, c)), R(i, c) = fma(-alpha_c, Q(i, c), R(i, c)) and
+// out[c] = sum_i R(i, c)^2 of the new R, on the columns of the mask (out as for the dot)
+hipError_t launch_pcg_update(double* X, int64_t ldx, double* R, int64_t ldr, const double* P, int64_t ldp,
+                             const double* Q, int64_t ldq, int64_t n, int nrhs, uint32_t mask, const PcgCoef& alpha,
+                             double* part, double* out, hipStream_t st);
+// P(i, c) = fma(beta_c, P(i, c), Z(i, c)), or Z(i, c) when first (P is then not read), on the
+// columns of the mask; pt (may be null): the new P in the product's 16-wide row-major form,
+// pt[SOLVE_RHS i + c], zero in the columns outside the mask
+hipError_t launch_pcg_dir(double* P, int64_t ldp, const double* Z, int64_t ldz, int64_t n, int nrhs, uint32_t mask,
+                          const PcgCoef& beta, bool first, double* pt, hipStream_t st);
+
 // Small fronts (m <= maxm <= 128): one workgroup per front, factored in registers
 // (4 x 4 tiles per thread); seq: one workgroup runs the fronts in order (a whole
 // small tree in postorder, CBs through HBM).

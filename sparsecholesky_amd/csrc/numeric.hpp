@@ -403,6 +403,17 @@ struct Numeric {
     double* d_rfR = nullptr;
     double* d_rfnorm = nullptr;        // SPMV_NQ + 1 rows of SOLVE_RHS norms, then the increment norm's partials
 
+    // preconditioned conjugate gradients (pcg.cpp; single-device handles), besides the above:
+    // the z, p and q panels (n x SOLVE_RHS, ld = n), the partials of the sums (PCG_NQ x
+    // SOLVE_RHS doubles per PCG_ROWS rows) and the scalar block (two results of PCG_NQ x
+    // SOLVE_RHS doubles), allocated at the first use, kept
+    bool pcg_ready = false;
+    double* d_pcgZ = nullptr;
+    double* d_pcgP = nullptr;
+    double* d_pcgQ = nullptr;
+    double* d_pcgpart = nullptr;
+    double* d_pcgscal = nullptr;
+
     std::string err;
 };
 
@@ -521,6 +532,16 @@ int64_t numeric_residual(Numeric& N, int32_t mode, int32_t nrhs, const double* A
 // multi-rank and emulated handles SC_ERR_NOTIMPL.  opt: validated by the caller.
 int64_t numeric_solve_refine(Numeric& N, const sc_refine_options& opt, int32_t nrhs, const double* Ax, const double* B,
                              int64_t ldb, double* X, int64_t ldx, sc_refine_info* info, bool host, const char* who);
+// X = A'^-1 B by conjugate gradients on the values Ax, preconditioned with the factor (pcg.cpp,
+// DESIGN.md section 9.6); arguments, values and status rules as numeric_solve_refine.  opt:
+// validated by the caller; with opt.use_x0 X holds the starting vectors on entry.
+int64_t numeric_solve_pcg(Numeric& N, const sc_pcg_options& opt, int32_t nrhs, const double* Ax, const double* B,
+                          int64_t ldb, double* X, int64_t ldx, sc_pcg_info* info, bool host, const char* who);
+// One vector kernel of the conjugate gradients alone on caller panels (device), synchronous;
+// include/sparsecholesky_debug.h has the contract.
+int64_t debug_pcg_vec(int32_t which, int32_t n, int32_t nrhs, uint32_t mask, const double* coef, double* dA,
+                      int64_t lda, double* dB, int64_t ldb, const double* dC, int64_t ldc, const double* dD, int64_t ldd,
+                      double* dT, double* out, std::string& err);
 // The kernels alone on a caller's structure (host arrays, validated: rp ascending from 0, ci
 // in [0, n), sp in [0, nval)) and values and panels (device pointers), synchronous: mode
 // SpmvMode; X, B, R, W column-major n x nrhs (nrhs <= SOLVE_RHS); W and norms (SPMV_NQ x

@@ -118,6 +118,41 @@ struct SolveCut {
 };
 void solve_cut_front(int32_t s, int w, int m, int k0, int64_t goff, SolveCut& C);
 
+// refine.cpp: what the products with A, the refinement and the conjugate gradients share
+// a device buffer for the length of one host call
+struct DevTemp {
+    void* p = nullptr;
+    ~DevTemp() {
+        if (p) (void)hipFree(p);
+    }
+    int64_t get(Numeric& N, size_t bytes) {
+        if (hipMalloc(&p, std::max<size_t>(bytes, 8)) != hipSuccess) {
+            p = nullptr;
+            N.err = "refinement: device allocation of a host call's staging failed";
+            return SC_ERR_DEVMEM;
+        }
+        return SC_OK;
+    }
+};
+// SC_OK on a single-device handle, else SC_ERR_NOTIMPL with who's name in N.err
+int64_t single_device(Numeric& N, const char* who);
+// single_device, the handle's device current, the gather structure of A and its panels built
+int64_t spmv_ensure(Numeric& N, const char* who);
+// the device values a call works with: the caller's (host ones staged), or, for null, the
+// copy the last sc_factor made
+int64_t device_values(Numeric& N, const double* Ax, bool host, DevTemp& stage, const double*& d_Ax,
+                      const char* who);
+// One pass over A for a panel of nr columns: X transposed into the handle's panel, then
+// Y = A X (mode SPMV_MUL) or R = B - A X; h (SPMV_NQ x SOLVE_RHS, may be null): the norms,
+// on the host when the call returns.
+int64_t spmv_panel(Numeric& N, int mode, const double* d_Ax, int nr, const double* X, int64_t ldx, const double* B,
+                   int64_t ldb, double* R, int64_t ldr, double* h);
+// the two backward errors of column c from a pass's norms (0 / 0 = 0)
+void backward_errors(const double* h, int c, double& bnorm, double& bcomp);
+// n x nrhs host array (ld) into a packed device buffer (copy = false: the buffer alone), and back
+int64_t stage_in(Numeric& N, DevTemp& t, const double* A, int64_t ld, int64_t n, int32_t nrhs, bool copy);
+int64_t stage_out(Numeric& N, const DevTemp& t, double* A, int64_t ld, int64_t n, int32_t nrhs);
+
 // dist.cpp
 hipError_t comm_launch(Numeric& N, const Launch& L);
 int64_t dist_min_info(Numeric& N, int32_t& info);

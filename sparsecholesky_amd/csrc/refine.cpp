@@ -25,22 +25,6 @@ namespace {
 
 constexpr double UNIT = 1.1102230246251565e-16;  // 2^-53
 
-// a device buffer for the length of one host call
-struct Temp {
-    void* p = nullptr;
-    ~Temp() {
-        if (p) (void)hipFree(p);
-    }
-    int64_t get(Numeric& N, size_t bytes) {
-        if (hipMalloc(&p, std::max<size_t>(bytes, 8)) != hipSuccess) {
-            p = nullptr;
-            N.err = "refinement: device allocation of a host call's staging failed";
-            return SC_ERR_DEVMEM;
-        }
-        return SC_OK;
-    }
-};
-
 // tasks of the row pass: every row at least one, a row longer than SPMV_CH one per chunk
 // with consecutive partial slots, and the list of those rows for the combine pass
 void spmv_tasks(int64_t n, const int64_t* rp, std::vector<SpmvTask>& task, std::vector<SpmvLong>& lrow,
@@ -59,11 +43,15 @@ void spmv_tasks(int64_t n, const int64_t* rp, std::vector<SpmvTask>& task, std::
     }
 }
 
+}  // namespace
+
 int64_t single_device(Numeric& N, const char* who) {
     if (N.owner.empty() && !N.emulated && N.R.size() == 1) return SC_OK;
     N.err = std::string(who) + ": products with A and refinement run on single-device handles only";
     return SC_ERR_NOTIMPL;
 }
+
+namespace {
 
 int64_t spmv_build(Numeric& N) {
     const Symbolic& S = *N.S;
@@ -117,6 +105,8 @@ int64_t spmv_build(Numeric& N) {
     return SC_OK;
 }
 
+}  // namespace
+
 int64_t spmv_ensure(Numeric& N, const char* who) {
     TRY(single_device(N, who));
     HIP_TRY(hipSetDevice(N.device));
@@ -125,7 +115,8 @@ int64_t spmv_ensure(Numeric& N, const char* who) {
 }
 
 // the device values a call works with: the caller's, or the copy the last sc_factor made
-int64_t device_values(Numeric& N, const double* Ax, bool host, Temp& stage, const double*& d_Ax, const char* who) {
+int64_t device_values(Numeric& N, const double* Ax, bool host, DevTemp& stage, const double*& d_Ax,
+                      const char* who) {
     const int64_t nnz = N.S->nnzA_in;
     if (!Ax) {
         if (nnz > 0 && (!N.d_Ax_owned || N.last_Ax != N.d_Ax_owned)) {
@@ -171,6 +162,8 @@ void backward_errors(const double* h, int c, double& bnorm, double& bcomp) {
     bnorm = (r == 0.0 && den == 0.0) ? 0.0 : r / den;
     bcomp = h[3 * SOLVE_RHS + c];
 }
+
+namespace {
 
 int64_t residual_device(Numeric& N, int32_t mode, int32_t nrhs, const double* d_Ax, const double* B, int64_t ldb,
                         const double* X, int64_t ldx, double* R, int64_t ldr, double* berr_norm, double* berr_comp) {
@@ -282,10 +275,12 @@ int64_t refine_device(Numeric& N, const sc_refine_options& opt, int32_t nrhs, co
     return SC_OK;
 }
 
+}  // namespace
+
 // n x nrhs host array (ld) into a packed device buffer.  Every staging copy runs on the
 // handle's stream, like the kernels that read it: the stream is non-blocking, so a copy on
 // the null stream would not be ordered with them.
-int64_t stage_in(Numeric& N, Temp& t, const double* A, int64_t ld, int64_t n, int32_t nrhs, bool copy) {
+int64_t stage_in(Numeric& N, DevTemp& t, const double* A, int64_t ld, int64_t n, int32_t nrhs, bool copy) {
     TRY(t.get(N, (size_t)n * nrhs * sizeof(double)));
     if (copy)
         HIP_TRY(hipMemcpy2DAsync(t.p, (size_t)n * sizeof(double), A, (size_t)ld * sizeof(double),
@@ -293,20 +288,18 @@ int64_t stage_in(Numeric& N, Temp& t, const double* A, int64_t ld, int64_t n, in
     return SC_OK;
 }
 
-int64_t stage_out(Numeric& N, const Temp& t, double* A, int64_t ld, int64_t n, int32_t nrhs) {
+int64_t stage_out(Numeric& N, const DevTemp& t, double* A, int64_t ld, int64_t n, int32_t nrhs) {
     HIP_TRY(hipMemcpy2DAsync(A, (size_t)ld * sizeof(double), t.p, (size_t)n * sizeof(double),
                              (size_t)n * sizeof(double), (size_t)nrhs, hipMemcpyDeviceToHost, N.stream));
     HIP_TRY(hipStreamSynchronize(N.stream));
     return SC_OK;
 }
 
-}  // namespace
-
 int64_t numeric_spmv(Numeric& N, int32_t nrhs, const double* Ax, const double* X, int64_t ldx, double* Y, int64_t ldy,
                      bool host, const char* who) {
     TRY(single_device(N, who));
     const int64_t n = N.S->n;
-    Temp ta, tx, ty;
+    DevTemp ta, tx, ty;
     const double* d_Ax = nullptr;
     TRY(device_values(N, Ax, host, ta, d_Ax, who));
     if (n == 0 || nrhs == 0) return SC_OK;
@@ -333,7 +326,7 @@ int64_t numeric_residual(Numeric& N, int32_t mode, int32_t nrhs, const double* A
                          bool host, const char* who) {
     TRY(single_device(N, who));
     const int64_t n = N.S->n;
-    Temp ta, tb, tx, tr;
+    DevTemp ta, tb, tx, tr;
     const double* d_Ax = nullptr;
     TRY(device_values(N, Ax, host, ta, d_Ax, who));
     if (nrhs == 0) return SC_OK;
@@ -361,7 +354,7 @@ int64_t numeric_solve_refine(Numeric& N, const sc_refine_options& opt, int32_t n
     const int64_t st = numeric_status(N);
     if (st != SC_OK) return st;
     const int64_t n = N.S->n;
-    Temp ta, tb, tx;
+    DevTemp ta, tb, tx;
     const double* d_Ax = nullptr;
     TRY(device_values(N, Ax, host, ta, d_Ax, who));
     if (nrhs == 0) return SC_OK;
