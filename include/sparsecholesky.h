@@ -34,7 +34,7 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define SC_VERSION 121 /* still 1.2.1, additive: conjugate gradients preconditioned with the factor sc_solve_pcg_*_multi / sc_default_pcg_options; still 1.2.1, additive: products with A, residuals and iterative refinement sc_spmv_structure / sc_spmv_*_multi / sc_residual_*_multi / sc_solve_refine_*_multi / sc_default_refine_options; still 1.2.1, additive: Schur complement sc_analyze_schur / sc_symbolic_schur / sc_schur_factor_* / sc_schur_matrix_* / sc_schur_condense_*_multi / sc_schur_expand_*_multi; still 1.2.1, additive: rank-k update / downdate sc_updown_check / sc_updown_host; still 1.2.1, additive: selected inversion sc_selinv / sc_selinv_diag_host / sc_selinv_diag_device / sc_selinv_export / sc_selinv_flops; still 1.2.1, additive: the factor operators sc_apply_host / sc_apply_device / sc_apply_host_multi / sc_apply_device_multi (enum sc_factor_op) and sc_logdet; still 1.2.1, additive: sc_solve_host_multi / sc_solve_device_multi (nrhs right-hand sides); 1.2.1:small merged fronts amalgamated past relax_wmax (different supernode partition of some inputs, same L); 1.2.0: persistent slab chain options removed; panel_prefactor, dist_local_pieces and SC_ORDER_AMD added; out-of-range lookahead / inner_order / ordering rejected */
+#define SC_VERSION 121 /* still 1.2.1, additive: eigenpairs nearest zero by block shift-invert Lanczos sc_eigs_host / sc_eigs_device / sc_default_eigs_options; still 1.2.1, additive: conjugate gradients preconditioned with the factor sc_solve_pcg_*_multi / sc_default_pcg_options; still 1.2.1, additive: products with A, residuals and iterative refinement sc_spmv_structure / sc_spmv_*_multi / sc_residual_*_multi / sc_solve_refine_*_multi / sc_default_refine_options; still 1.2.1, additive: Schur complement sc_analyze_schur / sc_symbolic_schur / sc_schur_factor_* / sc_schur_matrix_* / sc_schur_condense_*_multi / sc_schur_expand_*_multi; still 1.2.1, additive: rank-k update / downdate sc_updown_check / sc_updown_host; still 1.2.1, additive: selected inversion sc_selinv / sc_selinv_diag_host / sc_selinv_diag_device / sc_selinv_export / sc_selinv_flops; still 1.2.1, additive: the factor operators sc_apply_host / sc_apply_device / sc_apply_host_multi / sc_apply_device_multi (enum sc_factor_op) and sc_logdet; still 1.2.1, additive: sc_solve_host_multi / sc_solve_device_multi (nrhs right-hand sides); 1.2.1:small merged fronts amalgamated past relax_wmax (different supernode partition of some inputs, same L); 1.2.0: persistent slab chain options removed; panel_prefactor, dist_local_pieces and SC_ORDER_AMD added; out-of-range lookahead / inner_order / ordering rejected */
 
 enum sc_status {
     SC_OK = 0,
@@ -661,6 +661,93 @@ int64_t sc_solve_pcg_host_multi(sc_numeric* num, const sc_pcg_options* opt, int3
                                 const double* B, int64_t ldb, double* X, int64_t ldx, sc_pcg_info* info);
 int64_t sc_solve_pcg_device_multi(sc_numeric* num, const sc_pcg_options* opt, int32_t nrhs, const double* d_Ax,
                                   const double* d_B, int64_t ldb, double* d_X, int64_t ldx, sc_pcg_info* info);
+
+/* The eigenpairs of the factored matrix nearest zero, by block shift-invert Lanczos on the GPU:
+ * vibration and buckling modes with the stiffness factor, the Fiedler vector of a graph
+ * Laplacian, the slow modes of a precision matrix, lambda_min for cond_2 or the largest safe
+ * downdate.  The handle holds the factor of F = A - sigma I (the caller factored those values;
+ * sigma only shifts what is reported).  The call returns the nev eigenvalues of F nearest zero
+ * plus sigma -- the smallest of A when sigma = 0 -- ascending in lambda (host, nev doubles),
+ * and their eigenvectors as the columns of X (n x nev, leading dimension ldx >= n, A's own
+ * numbering, each of unit 2-norm).  Ax / d_Ax: the factored values, under the rules of the
+ * refinement entry points (NULL: the copy sc_factor made, legal only after sc_factor); they are
+ * used for the reported residuals alone, resid_i = |F x_i - x_i / theta_i|_2, so values other
+ * than the factored ones show there and not silently.
+ * The algorithm, with b = min(16, n) the block width (columns >= b of a panel do not exist for
+ * the kernels), u = 2^-53, and all panels n x b:
+ *   start block: use_x0 = 0: entry (i, c) = 2 v - 1 with v = (splitmix64(seed + (16 i + c + 1)
+ *     g) >> 11) 2^-53, g = 0x9E3779B97F4A7C15, z -> splitmix64(z): z = (z ^ z >> 30)
+ *     0xBF58476D1CE4E5B9; z = (z ^ z >> 27) 0x94D049BB133111EB; z ^ z >> 31 (64-bit wrapping): it
+ *     depends on seed, i and c alone.  use_x0 = 1: the first b columns of X0 (ldx0 >= n).
+ *   orth(W), twice: scale every column by 1 / sqrt of its Gram diagonal (0 for a zero column);
+ *     G = W^T W (Gram kernel); G = R^T R by Cholesky on the host (16 x 16), a column whose pivot
+ *     is <= 2 (n + 16) u or not finite is dropped (left out of R, its column of inv(R) zero: it
+ *     becomes a zero column of W); W <- W inv(R) (block-update kernel, in place).
+ *   V_0 = orth(start).  Step j = 0, 1, ..:
+ *     1. W = inv(F) V_j (sc_solve_device_multi's panel solve)
+ *     2. twice: H_i = V_i^T W for all i <= j (one Gram launch), W -= sum_i V_i H_i (one block-
+ *        update launch); the H of the two passes add up
+ *     3. column block j of T = that H, row block j its transpose, the diagonal block (H_j + H_j^T)
+ *        / 2: T is m x m, m = b (j + 1), symmetric, on the host
+ *     4. G = W^T W of the projected W
+ *     5. T = S diag(theta) S^T on the host (Householder tridiagonalisation, implicit QL); the
+ *        wanted pairs are the nev largest theta (fewer while m < nev: not converged)
+ *     6. est_i = sqrt(s_i^T G s_i), s_i the last b entries of S's column: the residual of
+ *        (theta_i, V s_i) for inv(F), needing no factor of G
+ *     stop when   est_i <= tol theta_i for every wanted pair,
+ *       or        j + 1 == max_blocks,
+ *       or        the space cannot grow: m + b > n, or W is rank-deficient -- a diagonal entry of
+ *                 G not positive, or a pivot <= 2 (n + 16) u in the Cholesky of G scaled to a unit
+ *                 diagonal (indistinguishable from the rounding of the Gram entries, gamma_n, and
+ *                 of the elimination, gamma_17);
+ *     else V_{j+1} = orth(W).
+ *   At the stop: X = sum_i V_i S_i over the wanted columns (one block-update launch per 16
+ *   pairs), lambda_i = sigma + 1 / theta_i, resid from one product with F and one sum pass.
+ * sc_eigs_info (nev entries, host, may be NULL), per pair: blocks = j + 1; est; resid; state
+ *   SC_EIGS_CONVERGED  est_i <= tol theta_i at the stop
+ *   SC_EIGS_MAXBLOCKS  not converged, and the block cap was reached
+ *   SC_EIGS_EXHAUSTED  not converged, and the space could not grow.
+ * With |x| = 1: resid = |F r| / theta <= |F| est / theta <= tol |F| for a converged pair (r =
+ * inv(F) x - theta x, |r| = est), and |lambda_i - an eigenvalue of A| <= resid_i.  A space that
+ * stops below nev columns (m + b > n with n no multiple of 16) has no Ritz pair for the last
+ * nev - m: they come back as lambda = +inf, x = 0, est = resid = +inf, not converged.
+ * Every sum has an order fixed by n and the block count alone and there are no atomics: results
+ * repeat bit for bit across calls and handles.  The basis is kept whole (no restarts), so
+ * max_blocks bounds the memory as well as the work; the host eigensolver costs O(m^3) per step.
+ * Status: as sc_solve_pcg_*_multi -- SC_ERR_STATE before a factorization; a failed
+ * factorization returns its status > 0 and writes nothing; multi-rank and emulated handles
+ * SC_ERR_NOTIMPL with a message; nev == 0 or n == 0: SC_OK, nothing touched.  SC_ERR_ARG with the
+ * entry point's name in sc_last_error for a null handle, a null lambda or X (or X0 with use_x0),
+ * nev < 0, nev > min(n, 16 max_blocks), ldx < n, ldx0 < n with use_x0, an options struct of the
+ * wrong struct_size, max_blocks outside 1..32, tol outside [0, 1), use_x0 other than 0 or 1,
+ * and a sigma that is not finite; also, with a message, when the QL iteration on T does not
+ * converge in 60 sweeps (a start block or a factor that is not finite).  NULL options: the
+ * defaults.  Calls are synchronous.
+ * Device memory, counted in sc_numeric_memory info[0], allocated at the first call and kept
+ * until sc_free_numeric, besides what the refinement section lists (n at least 1 below):
+ *   (max_blocks + 1) x 128 n      the basis; replaced by a larger one, with the next two, when
+ *                                 a later call asks for more blocks
+ *   2048 max_blocks per 1024 rows (rounded up, at least one)    Gram partials
+ *   4096 max_blocks               Gram results and update coefficients
+ *   128 n                         the residual panel */
+enum { SC_EIGS_CONVERGED = 0, SC_EIGS_MAXBLOCKS = 1, SC_EIGS_EXHAUSTED = 2 };
+typedef struct sc_eigs_options {
+    int32_t struct_size; /* sizeof(sc_eigs_options), set by sc_default_eigs_options */
+    int32_t max_blocks;  /* 32; basis blocks of 16 columns at most, 1..32 */
+    int32_t use_x0;      /* 0: the library's start block; 1: the first min(16, n) columns of X0 */
+    uint64_t seed;       /* 1; the start block when use_x0 = 0 */
+    double tol;          /* 1e-10, in [0, 1) */
+    double sigma;        /* 0; the handle holds the factor of A - sigma I; lambda = sigma + 1 / theta */
+} sc_eigs_options;
+typedef struct sc_eigs_info {
+    int32_t state, blocks;
+    double est, resid;
+} sc_eigs_info;
+void sc_default_eigs_options(sc_eigs_options* opt);
+int64_t sc_eigs_host(sc_numeric* num, const sc_eigs_options* opt, int32_t nev, const double* Ax, const double* X0,
+                     int64_t ldx0, double* lambda, double* X, int64_t ldx, sc_eigs_info* info);
+int64_t sc_eigs_device(sc_numeric* num, const sc_eigs_options* opt, int32_t nev, const double* d_Ax,
+                       const double* d_X0, int64_t ldx0, double* lambda, double* d_X, int64_t ldx, sc_eigs_info* info);
 
 /* ---------------- reference-API helpers (host) ----------------
  * Each mirrors one reference function, with int64 column pointers. */

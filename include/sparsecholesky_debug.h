@@ -128,6 +128,33 @@ int64_t sc_debug_spmv(int32_t mode, int32_t n, const int64_t* rp, const int32_t*
 int64_t sc_debug_pcg_vec(int32_t which, int32_t n, int32_t nrhs, uint32_t mask, const double* coef, double* d_A,
                          int64_t lda, double* d_B, int64_t ldb, const double* d_C, int64_t ldc, const double* d_D,
                          int64_t ldd, double* d_T, double* out);
+/* The two panel kernels of the eigensolver alone (no handle) on caller panels in device memory.
+ * A panel is n x b column-major (b <= 16, leading dimension >= n), a basis nb <= 64 panels
+ * vstride doubles apart (vstride >= b ldv when nb > 1); a tile is a 16 x 16 matrix in 256 host
+ * doubles, M(a, c) at a + 16 c.  Rows >= n and columns >= b of a panel are neither read nor
+ * written.
+ *   gram:   out (nb tiles, host) = V_i^T W, i < nb; entries with a or c >= b are zero.  d_V may
+ *           be d_W.  A block's tile has the same bits whatever nb and its place in the basis.
+ *   update: Out = beta W + sum_{i < nb} V_i C_i with Out and W n x bc (bc <= 16), C nb tiles on
+ *           the host (entries with a >= b or c >= bc are not read); beta == 0: d_W is not read
+ *           and may be NULL; nb == 0 or b == 0: Out = beta W.  d_Out may be d_W and may be a block
+ *           of d_V (a wave reads its rows of every operand before it writes them).
+ * Both repeat bit for bit.  Everything is validated before a launch: n < 0, b or bc outside
+ * [0, 16], nb outside [0, 64], a null array the kernel needs, a leading dimension below n or
+ * overlapping blocks return SC_ERR_ARG with a message; gram with n == 0 or b == 0: SC_OK, out
+ * zero; update with n == 0 or bc == 0: SC_OK.  Synchronous. */
+int64_t sc_debug_eigs_gram(int32_t n, int32_t b, int32_t nb, const double* d_V, int64_t ldv, int64_t vstride,
+                           const double* d_W, int64_t ldw, double* out);
+int64_t sc_debug_eigs_update(int32_t n, int32_t b, int32_t bc, int32_t nb, double beta, double* d_Out, int64_t ldo,
+                             const double* d_W, int64_t ldw, const double* d_V, int64_t ldv, int64_t vstride,
+                             const double* C);
+/* The eigensolver's host dense algebra alone (no GPU).  which 0: A (m x m row-major, symmetric,
+ * m <= 512) is replaced by its unit eigenvectors (columns), d (m) gets the eigenvalues
+ * ascending; returns 0, or 1 when the QL iteration did not converge.  which 1: A is a tile G
+ * whose leading m x m part (m <= 16; upper triangle read) is factored G = R^T R with the pivot
+ * threshold d[0]; d (256 doubles) gets the tile inv(R), the columns of dropped pivots zero;
+ * returns the number of dropped columns. */
+int64_t sc_debug_eigs_dense(int32_t which, int32_t m, double* A, double* d);
 /* Chain launches (runs of single small-front levels): enable = 1 makes the next
  * eager factorizations record 8 shader-clock stamps per chained front (phase
  * boundaries); enable = 0 copies up to cap of them to out.  Returns the count. */

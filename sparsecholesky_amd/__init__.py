@@ -49,6 +49,7 @@ __all__ = [
     "RefineOptions", "RefineInfo", "SC_RESIDUAL_FP64", "SC_RESIDUAL_DD",
     "SC_REFINE_CONVERGED", "SC_REFINE_STALLED", "SC_REFINE_MAXITER", "SC_REFINE_DIVERGED",
     "PcgOptions", "PcgInfo", "SC_PCG_CONVERGED", "SC_PCG_MAXITER", "SC_PCG_BREAKDOWN",
+    "EigsOptions", "EigsInfo", "SC_EIGS_CONVERGED", "SC_EIGS_MAXBLOCKS", "SC_EIGS_EXHAUSTED",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -62,6 +63,8 @@ SC_RESIDUAL_FP64, SC_RESIDUAL_DD = 0, 1
 SC_REFINE_CONVERGED, SC_REFINE_STALLED, SC_REFINE_MAXITER, SC_REFINE_DIVERGED = range(4)
 # the states a column of Numeric.solve_pcg ends in
 SC_PCG_CONVERGED, SC_PCG_MAXITER, SC_PCG_BREAKDOWN = range(3)
+# the states an eigenpair of Numeric.eigsh ends in
+SC_EIGS_CONVERGED, SC_EIGS_MAXBLOCKS, SC_EIGS_EXHAUSTED = range(3)
 _RESIDUAL_MODES = {"fp64": SC_RESIDUAL_FP64, "dd": SC_RESIDUAL_DD}
 _STATUS = {
     -1: "invalid argument", -2: "host allocation failed", -3: "HIP runtime error",
@@ -107,6 +110,15 @@ class PcgOptions(C.Structure):
 class PcgInfo(C.Structure):
     _fields_ = [("iters", C.c_int32), ("state", C.c_int32), ("relres", C.c_double), ("relres_true", C.c_double),
                 ("berr_norm", C.c_double), ("berr_comp", C.c_double)]
+
+
+class EigsOptions(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("max_blocks", C.c_int32), ("use_x0", C.c_int32), ("seed", C.c_uint64),
+                ("tol", C.c_double), ("sigma", C.c_double)]
+
+
+class EigsInfo(C.Structure):
+    _fields_ = [("state", C.c_int32), ("blocks", C.c_int32), ("est", C.c_double), ("resid", C.c_double)]
 
 
 class SymbolicStats(C.Structure):
@@ -194,6 +206,9 @@ _SIGS = [
     ("sc_default_pcg_options", None, [C.POINTER(PcgOptions)]),
     ("sc_solve_pcg_host_multi", _I64, [_P, C.POINTER(PcgOptions), _I32, _P, _P, _I64, _P, _I64, _P]),
     ("sc_solve_pcg_device_multi", _I64, [_P, C.POINTER(PcgOptions), _I32, _P, _P, _I64, _P, _I64, _P]),
+    ("sc_default_eigs_options", None, [C.POINTER(EigsOptions)]),
+    ("sc_eigs_host", _I64, [_P, C.POINTER(EigsOptions), _I32, _P, _P, _I64, _P, _P, _I64, _P]),
+    ("sc_eigs_device", _I64, [_P, C.POINTER(EigsOptions), _I32, _P, _P, _I64, _P, _P, _I64, _P]),
     ("sc_etree", _I64, [_I64, _P, _P, _P]),
     ("sc_post_order", _I64, [_I64, _P, _P]),
     ("sc_col_count", _I64, [_I64, _P, _P, _P, _P, _P]),
@@ -225,6 +240,9 @@ _SIGS = [
     ("sc_debug_solve_gather", _I64, [_I32, _I32, _I32, _I32, _P, _P, _P, _P, _P]),
     ("sc_debug_spmv", _I64, [_I32, _I32, _P, _P, _P, _I64, _P, _I32, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _P]),
     ("sc_debug_pcg_vec", _I64, [_I32, _I32, _I32, C.c_uint32, _P, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _P]),
+    ("sc_debug_eigs_gram", _I64, [_I32, _I32, _I32, _P, _I64, _I64, _P, _I64, _P]),
+    ("sc_debug_eigs_update", _I64, [_I32, _I32, _I32, _I32, _D, _P, _I64, _P, _I64, _P, _I64, _I64, _P]),
+    ("sc_debug_eigs_dense", _I64, [_I32, _I32, _P, _P]),
     ("sc_debug_bench", _I64, [_I32, _I32, _I32, _I32, _I32, C.POINTER(_D)]),
     ("sc_device_count", _I64, []),
     ("sc_debug_chain_stamps", _I64, [_P, _I32, _P, _I64]),
@@ -1210,6 +1228,83 @@ class Numeric:
         if st > 0:
             raise LibraryError(f"solve_pcg_device_multi: A is not positive definite (column {st})")
         return self._pcg_info(info, nrhs, False)
+
+    @staticmethod
+    def _eigs_options(sigma: float, tol: float, max_blocks: int, use_x0: bool, seed: int) -> EigsOptions:
+        o = EigsOptions()
+        lib().sc_default_eigs_options(C.byref(o))
+        o.sigma, o.tol, o.max_blocks, o.use_x0, o.seed = sigma, tol, max_blocks, int(use_x0), seed
+        return o
+
+    @staticmethod
+    def _eigs_info(info, k: int) -> dict:
+        return {f: np.array([getattr(info[j], f) for j in range(k)]) for f, _ in EigsInfo._fields_}
+
+    def eigsh(self, nev: int, *, sigma: float = 0.0, tol: float = 1e-10, max_blocks: int = 32, X0=None, seed: int = 1,
+              values=None, return_info: bool = False):
+        """(lam, X): the ``nev`` eigenvalues nearest ``sigma`` of the matrix whose shifted form A -
+        sigma I this handle holds the factor of (the smallest of A for ``sigma = 0``), ascending,
+        and their unit eigenvectors as the columns of X (n, nev), by block shift-invert Lanczos
+        on the GPU with at most ``max_blocks`` basis blocks of 16 columns.  ``X0``: a start block
+        (n, k), k >= min(16, n), whose first min(16, n) columns are used (``None``: the library's
+        own, a function of ``seed``).  ``values``: the factored values, for the reported
+        residuals (``None``: those of the last :meth:`factor`).  With ``return_info`` a third
+        result: a dict of arrays over the pairs -- state (SC_EIGS_*), blocks, est, resid
+        (sc_eigs_host)."""
+        n = self.symb.n
+        X = np.zeros((n, nev), dtype=np.float64, order="F")
+        lam = np.zeros(max(nev, 0), dtype=np.float64)
+        info = (EigsInfo * max(nev, 1))()
+        X0f, ld0 = None, max(n, 1)
+        if X0 is not None:
+            X0f, _ = self._panel_in(X0, "eigsh")
+            if X0f.shape[1] < min(16, n):
+                raise ValueError(f"eigsh: X0 has {X0f.shape[1]} columns, the start block needs {min(16, n)}")
+        o = self._eigs_options(sigma, tol, max_blocks, X0 is not None, seed)
+        st = _check(lib().sc_eigs_host(self.h, C.byref(o), nev, _ptr(self._values(values)), _ptr(X0f), ld0, _ptr(lam),
+                                       _ptr(X), max(n, 1), info), "eigsh")
+        if st > 0:
+            raise LibraryError(f"eigsh: A is not positive definite (column {st})")
+        return (lam, X, self._eigs_info(info, nev)) if return_info else (lam, X)
+
+    def eigsh_device(self, nev: int, *, sigma: float = 0.0, tol: float = 1e-10, max_blocks: int = 32, X0=None,
+                     seed: int = 1, values=None, return_info: bool = False):
+        """:meth:`eigsh` with torch tensors on the handle's device: ``values`` a float64 vector,
+        ``X0`` an (n, k) float64 tensor (copied unless it is column-major already).  Returns
+        lam (a numpy array: the eigenvalues are decided on the host) and X, an (n, nev)
+        column-major float64 tensor on the device of the tensors passed (the current one when
+        there is none) (sc_eigs_device)."""
+        import torch
+
+        n = self.symb.n
+        dev = next((t.device for t in (X0, values) if isinstance(t, torch.Tensor)), torch.device("cuda"))
+
+        def check(t, what):
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64):
+                raise ValueError(f"eigsh_device: {what} must be a float64 tensor on the GPU")
+
+        Xt = torch.zeros((max(nev, 0), n), dtype=torch.float64, device=dev)  # column c of X is row c
+        lam = np.zeros(max(nev, 0), dtype=np.float64)
+        info = (EigsInfo * max(nev, 1))()
+        p0, pv = None, None
+        if X0 is not None:
+            check(X0, "X0")
+            if X0.ndim != 2 or X0.shape[0] != n or X0.shape[1] < min(16, n):
+                raise ValueError(f"eigsh_device: X0 is {tuple(X0.shape)}, the start block is ({n}, {min(16, n)})")
+            X0t = X0.t().contiguous()
+            p0 = X0t.data_ptr()
+        if values is not None:
+            check(values, "values")
+            values = values.contiguous()
+            pv = values.data_ptr()
+        o = self._eigs_options(sigma, tol, max_blocks, X0 is not None, seed)
+        st = _check(lib().sc_eigs_device(self.h, C.byref(o), nev, C.c_void_p(pv), C.c_void_p(p0), max(n, 1), _ptr(lam),
+                                         C.c_void_p(Xt.data_ptr() if nev > 0 and n > 0 else None), max(n, 1), info),
+                    "eigsh_device")
+        if st > 0:
+            raise LibraryError(f"eigsh_device: A is not positive definite (column {st})")
+        X = Xt.t()
+        return (lam, X, self._eigs_info(info, nev)) if return_info else (lam, X)
 
     def selinv(self) -> int:
         """Selected inversion: every entry of A^-1 on the pattern of L into the handle's Z

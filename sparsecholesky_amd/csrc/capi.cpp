@@ -973,6 +973,100 @@ int64_t sc_solve_pcg_device_multi(sc_numeric* num, const sc_pcg_options* opt, in
     return pcg_multi(num, opt, nrhs, d_Ax, d_B, ldb, d_X, ldx, info, false, "sc_solve_pcg_device_multi");
 }
 
+// ---- eigenpairs nearest zero by block shift-invert Lanczos ----
+void sc_default_eigs_options(sc_eigs_options* opt) {
+    if (!opt) return;
+    std::memset(opt, 0, sizeof(*opt));
+    opt->struct_size = (int32_t)sizeof(sc_eigs_options);
+    opt->max_blocks = 32;
+    opt->use_x0 = 0;
+    opt->seed = 1;
+    opt->tol = 1e-10;
+    opt->sigma = 0.0;
+}
+
+static int64_t eigs_entry(sc_numeric* num, const sc_eigs_options* opt, int32_t nev, const double* Ax, const double* X0,
+                          int64_t ldx0, double* lambda, double* X, int64_t ldx, sc_eigs_info* info, bool host,
+                          const char* who) {
+    sc_eigs_options o;
+    sc_default_eigs_options(&o);
+    std::string bad;
+    if (!num || !num->N)
+        bad = "null handle";
+    else if (opt && opt->struct_size != (int32_t)sizeof(sc_eigs_options))
+        bad = "sc_eigs_options.struct_size does not match this library's sizeof(sc_eigs_options): initialise the "
+              "options with sc_default_eigs_options()";
+    else {
+        if (opt) o = *opt;
+        const int64_t n = num->N->S->n;
+        if (o.max_blocks < 1 || o.max_blocks > 32)
+            bad = "max_blocks outside 1..32";
+        else if (!(o.tol >= 0.0 && o.tol < 1.0))
+            bad = "tol outside [0, 1)";
+        else if (o.use_x0 != 0 && o.use_x0 != 1)
+            bad = "use_x0 is neither 0 nor 1";
+        else if (!std::isfinite(o.sigma))
+            bad = "sigma is not finite";
+        else if (nev < 0)
+            bad = "nev < 0";
+        else if (nev > std::min<int64_t>(n, (int64_t)16 * o.max_blocks))
+            bad = "nev > min(n, 16 max_blocks)";
+        else if (ldx < n)
+            bad = "leading dimension of X below n";
+        else if (o.use_x0 && ldx0 < n)
+            bad = "leading dimension of X0 below n";
+        else if (nev > 0 && !lambda)
+            bad = "null lambda";
+        else if (nev > 0 && !X)
+            bad = "null X";
+        else if (nev > 0 && o.use_x0 && !X0)
+            bad = "null X0";
+    }
+    if (!bad.empty()) {
+        g_last_error = std::string(who) + ": " + bad;
+        return SC_ERR_ARG;
+    }
+    int64_t rc;
+    try {
+        rc = sc::numeric_eigs(*num->N, o, nev, Ax, X0, ldx0, lambda, X, ldx, info, host, who);
+    } catch (const std::bad_alloc&) {
+        return SC_ERR_NOMEM;
+    }
+    if (rc < 0) g_last_error = num->N->err;
+    return rc;
+}
+
+int64_t sc_eigs_host(sc_numeric* num, const sc_eigs_options* opt, int32_t nev, const double* Ax, const double* X0,
+                     int64_t ldx0, double* lambda, double* X, int64_t ldx, sc_eigs_info* info) {
+    return eigs_entry(num, opt, nev, Ax, X0, ldx0, lambda, X, ldx, info, true, "sc_eigs_host");
+}
+int64_t sc_eigs_device(sc_numeric* num, const sc_eigs_options* opt, int32_t nev, const double* d_Ax, const double* d_X0,
+                       int64_t ldx0, double* lambda, double* d_X, int64_t ldx, sc_eigs_info* info) {
+    return eigs_entry(num, opt, nev, d_Ax, d_X0, ldx0, lambda, d_X, ldx, info, false, "sc_eigs_device");
+}
+
+int64_t sc_debug_eigs_gram(int32_t n, int32_t b, int32_t nb, const double* d_V, int64_t ldv, int64_t vstride,
+                           const double* d_W, int64_t ldw, double* out) {
+    return sc::debug_eigs_gram(n, b, nb, d_V, ldv, vstride, d_W, ldw, out, g_last_error);
+}
+int64_t sc_debug_eigs_update(int32_t n, int32_t b, int32_t bc, int32_t nb, double beta, double* d_Out, int64_t ldo,
+                             const double* d_W, int64_t ldw, const double* d_V, int64_t ldv, int64_t vstride,
+                             const double* C) {
+    return sc::debug_eigs_update(n, b, bc, nb, beta, d_Out, ldo, d_W, ldw, d_V, ldv, vstride, C, g_last_error);
+}
+int64_t sc_debug_eigs_dense(int32_t which, int32_t m, double* A, double* d) {
+    if (m < 0 || (m > 0 && (!A || !d)) || which < 0 || which > 1 || (which == 0 && m > 512) || (which == 1 && m > 16)) {
+        g_last_error = "sc_debug_eigs_dense: unknown operation, m out of range or a null array";
+        return SC_ERR_ARG;
+    }
+    try {
+        if (which == 0) return sc::eigs_sym_eig(m, A, d) ? 0 : 1;
+        return sc::eigs_chol_inv(A, m, d[0], d);
+    } catch (const std::bad_alloc&) {
+        return SC_ERR_NOMEM;
+    }
+}
+
 int64_t sc_debug_pcg_vec(int32_t which, int32_t n, int32_t nrhs, uint32_t mask, const double* coef, double* d_A,
                          int64_t lda, double* d_B, int64_t ldb, const double* d_C, int64_t ldc, const double* d_D,
                          int64_t ldd, double* d_T, double* out) {

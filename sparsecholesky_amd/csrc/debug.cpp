@@ -1,7 +1,8 @@
 // Debug and microbenchmark hooks (sc_debug_syrk, sc_debug_syrk_ex, sc_debug_panel,
 // sc_debug_updown_block, sc_debug_solve_step, sc_debug_solve_gather, sc_debug_pcg_vec,
-// sc_debug_bench): the SYRK, panel, update / downdate, solve / factor-product and conjugate-
-// gradient vector kernels on caller data, kernel ceilings on synthetic operands.
+// sc_debug_eigs_gram, sc_debug_eigs_update, sc_debug_bench): the SYRK, panel, update /
+// downdate, solve / factor-product, conjugate-gradient vector and eigensolver panel kernels on
+// caller data, kernel ceilings on synthetic operands.
 #include "numeric_impl.hpp"
 
 namespace sc {
@@ -37,6 +38,69 @@ int64_t debug_pcg_vec(int32_t which, int32_t n, int32_t nrhs, uint32_t mask, con
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e == hipSuccess && sums) e = hipMemcpy(out, scratch + npart, nout * sizeof(double), hipMemcpyDeviceToHost);
     (void)hipFree(scratch);
+    return e == hipSuccess ? SC_OK : SC_ERR_HIP;
+}
+
+namespace {
+
+// what the two eigensolver hooks check alike; null: fine
+const char* eigs_panels_bad(int32_t n, int32_t b, int32_t nb, const double* dV, int64_t ldv, int64_t vstride) {
+    if (n < 0 || b < 0 || b > SOLVE_RHS) return "n < 0 or b outside [0, 16]";
+    if (nb < 0 || nb > 64) return "nb outside [0, 64]";
+    if (n == 0 || b == 0 || nb == 0) return nullptr;
+    if (!dV) return "null array";
+    if (ldv < n) return "leading dimension below n";
+    if (nb > 1 && vstride < (int64_t)b * ldv) return "blocks of V closer than b columns";
+    return nullptr;
+}
+
+}  // namespace
+
+int64_t debug_eigs_gram(int32_t n, int32_t b, int32_t nb, const double* dV, int64_t ldv, int64_t vstride,
+                        const double* dW, int64_t ldw, double* out, std::string& err) {
+    auto bad = [&](const char* what) {
+        err = std::string("sc_debug_eigs_gram: ") + what;
+        return (int64_t)SC_ERR_ARG;
+    };
+    if (const char* w = eigs_panels_bad(n, b, nb, dV, ldv, vstride)) return bad(w);
+    if (nb == 0) return SC_OK;
+    if (!out) return bad("null array");
+    std::fill(out, out + (size_t)nb * EIGS_TILE, 0.0);
+    if (n == 0 || b == 0) return SC_OK;
+    if (!dW) return bad("null array");
+    if (ldw < n) return bad("leading dimension below n");
+    double* scratch = nullptr;
+    const size_t npart = (size_t)eigs_groups(n) * nb * EIGS_TILE, nout = (size_t)nb * EIGS_TILE;
+    if (hipMalloc((void**)&scratch, (npart + nout) * sizeof(double)) != hipSuccess) return SC_ERR_DEVMEM;
+    hipError_t e = launch_eigs_gram(dV, ldv, vstride, nb, dW, ldw, n, b, scratch, scratch + npart, nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(out, scratch + npart, nout * sizeof(double), hipMemcpyDeviceToHost);
+    (void)hipFree(scratch);
+    return e == hipSuccess ? SC_OK : SC_ERR_HIP;
+}
+
+int64_t debug_eigs_update(int32_t n, int32_t b, int32_t bc, int32_t nb, double beta, double* dOut, int64_t ldo,
+                          const double* dW, int64_t ldw, const double* dV, int64_t ldv, int64_t vstride,
+                          const double* C, std::string& err) {
+    auto bad = [&](const char* what) {
+        err = std::string("sc_debug_eigs_update: ") + what;
+        return (int64_t)SC_ERR_ARG;
+    };
+    if (const char* w = eigs_panels_bad(n, b, nb, dV, ldv, vstride)) return bad(w);
+    if (bc < 0 || bc > SOLVE_RHS) return bad("bc outside [0, 16]");
+    if (n == 0 || bc == 0) return SC_OK;
+    if (!dOut || (beta != 0.0 && !dW) || (nb > 0 && b > 0 && !C)) return bad("null array");
+    if (ldo < n || (beta != 0.0 && ldw < n)) return bad("leading dimension below n");
+    double* dC = nullptr;
+    const size_t nc = (size_t)std::max(nb, 1) * EIGS_TILE * sizeof(double);
+    if (hipMalloc((void**)&dC, nc) != hipSuccess) return SC_ERR_DEVMEM;
+    hipError_t e = nb > 0 && b > 0 ? hipMemcpy(dC, C, (size_t)nb * EIGS_TILE * sizeof(double), hipMemcpyHostToDevice)
+                                   : hipSuccess;
+    // no block, or blocks of no column: the sum is empty
+    if (e == hipSuccess)
+        e = launch_eigs_update(dOut, ldo, beta, dW, ldw, dV, ldv, vstride, b > 0 ? nb : 0, dC, n, b, bc, nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    (void)hipFree(dC);
     return e == hipSuccess ? SC_OK : SC_ERR_HIP;
 }
 

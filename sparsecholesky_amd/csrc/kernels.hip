@@ -4135,4 +4135,188 @@ hipError_t launch_pcg_dir(double* P, int64_t ldp, const double* Z, int64_t ldz, 
     return hipGetLastError();
 }
 
+// ---- dense algebra on tall panels for the block Lanczos eigensolver (kernels.hpp has the contracts) ----
+constexpr int EIGS_CH = 256;          // rows a workgroup stages at a time: one per thread
+constexpr int EIGS_NCH = EIGS_ROWS / EIGS_CH;
+constexpr int EIGS_LD = EIGS_CH + 4;  // LDS row of a staged column: lanes (il, kq) read il LD + kq, 2 per bank pair
+
+// rows [r0, r0 + EIGS_CH) of an n x b panel: thread t its row t of every column, zeros outside
+__device__ __forceinline__ void eigs_rows_in(double (&v)[SOLVE_RHS], const double* P, int64_t ld, int64_t r0, int64_t n,
+                                             int b) {
+    const int64_t row = r0 + threadIdx.x;
+#pragma unroll
+    for (int c = 0; c < SOLVE_RHS; ++c) v[c] = (row < n && c < b) ? P[row + (int64_t)c * ld] : 0.0;
+}
+
+__global__ __launch_bounds__(256) void eigs_gram_kernel(const double* V, int64_t ldv, int64_t vstride, int nb,
+                                                        const double* W, int64_t ldw, int64_t n, int b,
+                                                        double* __restrict__ part) {
+    __shared__ double Ts[SOLVE_RHS][EIGS_LD];
+    __shared__ double red[4][EIGS_TILE];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, il = lane & 15, kq = lane >> 4;
+    const int64_t r0 = (int64_t)blockIdx.x * EIGS_ROWS;
+    double v[SOLVE_RHS];
+    // W's rows as the B operand: chunk q, K step s is row r0 + EIGS_CH q + 64 wv + 4 s + kq, column il
+    double wb[EIGS_NCH][16];
+    const int nq = (int)min((int64_t)EIGS_NCH, (n - r0 + EIGS_CH - 1) / EIGS_CH);  // chunks below n, >= 1
+#pragma unroll
+    for (int q = 0; q < EIGS_NCH; ++q) {
+        if (q >= nq) continue;  // uniform over the workgroup: the chunk lies past n
+        eigs_rows_in(v, W, ldw, r0 + EIGS_CH * q, n, b);
+        __syncthreads();
+#pragma unroll
+        for (int c = 0; c < SOLVE_RHS; ++c) Ts[c][tid] = v[c];
+        __syncthreads();
+#pragma unroll
+        for (int s = 0; s < 16; ++s) wb[q][s] = Ts[il][64 * wv + 4 * s + kq];
+    }
+    eigs_rows_in(v, V, ldv, r0, n, b);
+    for (int i = 0; i < nb; ++i) {
+        const double* Vi = V + (int64_t)i * vstride;
+        double4_t acc = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int q = 0; q < EIGS_NCH; ++q) {
+            if (q >= nq) continue;
+            __syncthreads();
+#pragma unroll
+            for (int c = 0; c < SOLVE_RHS; ++c) Ts[c][tid] = v[c];
+            __syncthreads();
+            // the next chunk's loads go out before this one's products
+            if (q + 1 < nq)
+                eigs_rows_in(v, Vi, ldv, r0 + EIGS_CH * (q + 1), n, b);
+            else if (i + 1 < nb)
+                eigs_rows_in(v, Vi + vstride, ldv, r0, n, b);
+#pragma unroll
+            for (int s = 0; s < 16; ++s)
+                acc = __builtin_amdgcn_mfma_f64_16x16x4f64(Ts[il][64 * wv + 4 * s + kq], wb[q][s], acc, 0, 0, 0);
+        }
+#pragma unroll
+        for (int g = 0; g < 4; ++g) red[wv][(kq + 4 * g) + 16 * il] = acc[g];
+        __syncthreads();
+        part[((int64_t)blockIdx.x * nb + i) * EIGS_TILE + tid] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+    }
+}
+
+// out[i] = the partial tiles of block i added in workgroup order
+__global__ __launch_bounds__(256) void eigs_gram_final_kernel(const double* __restrict__ part, int64_t nslots, int nb,
+                                                              double* __restrict__ out) {
+    const int i = blockIdx.x, e = threadIdx.x;
+    const double* p = part + (int64_t)i * EIGS_TILE + e;
+    const int64_t step = (int64_t)nb * EIGS_TILE;
+    double v = 0.0;
+    int64_t s = 0;
+    for (; s + 16 <= nslots; s += 16) {  // 16 loads in flight, added in order
+        double t[16];
+#pragma unroll
+        for (int k = 0; k < 16; ++k) t[k] = p[(s + k) * step];
+#pragma unroll
+        for (int k = 0; k < 16; ++k) v += t[k];
+    }
+    for (; s < nslots; ++s) v += p[s * step];
+    out[(int64_t)i * EIGS_TILE + e] = v;
+}
+
+constexpr int EIGS_UT = 4;  // 16-row steps a wave keeps in flight
+__global__ __launch_bounds__(256) void eigs_update_kernel(double* Out, int64_t ldo, double beta, const double* W,
+                                                          int64_t ldw, const double* V, int64_t ldv, int64_t vstride,
+                                                          int nb, const double* __restrict__ C, int64_t n, int b,
+                                                          int bc) {
+    const int lane = threadIdx.x & 63, il = lane & 15, kq = lane >> 4;
+    const int64_t r0 = (int64_t)blockIdx.x * (64 * EIGS_UT) + 16 * EIGS_UT * wave_id();
+    if (r0 >= n) return;  // wave-uniform
+    // the product transposed, D(c, r) = sum_a C(a, c) V(r, a): this lane holds rows r0 + 16 t + il,
+    // columns kq + 4 g of the result
+    double4_t acc[EIGS_UT];
+#pragma unroll
+    for (int t = 0; t < EIGS_UT; ++t) {
+        const int64_t row = r0 + 16 * t + il;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const int c = kq + 4 * g;
+            acc[t][g] = (beta != 0.0 && row < n && c < bc) ? beta * W[row + (int64_t)c * ldw] : 0.0;
+        }
+    }
+    // this lane's operands of block i: C_i(4 s + kq, il) and V_i(r0 + 16 t + il, 4 s + kq)
+    auto operands = [&](int i, double (&cv)[4], double (&x)[EIGS_UT][4]) {
+        const double* Vi = V + (int64_t)i * vstride;
+        const double* Ci = C + (int64_t)i * EIGS_TILE;
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            const int a = 4 * s + kq;
+            cv[s] = (a < b && il < bc) ? Ci[a + 16 * il] : 0.0;
+#pragma unroll
+            for (int t = 0; t < EIGS_UT; ++t) {
+                const int64_t row = r0 + 16 * t + il;
+                x[t][s] = (row < n && a < b) ? Vi[row + (int64_t)a * ldv] : 0.0;
+            }
+        }
+    };
+    double cv[4] = {}, x[EIGS_UT][4] = {}, cvn[4] = {}, xn[EIGS_UT][4] = {};
+    if (nb > 0) operands(0, cv, x);
+    for (int i = 0; i < nb; ++i) {
+        if (i + 1 < nb) operands(i + 1, cvn, xn);  // the next block's loads go out before this one's products
+#pragma unroll
+        for (int t = 0; t < EIGS_UT; ++t)
+#pragma unroll
+            for (int s = 0; s < 4; ++s) acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(cv[s], x[t][s], acc[t], 0, 0, 0);
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            cv[s] = cvn[s];
+#pragma unroll
+            for (int t = 0; t < EIGS_UT; ++t) x[t][s] = xn[t][s];
+        }
+    }
+#pragma unroll
+    for (int t = 0; t < EIGS_UT; ++t) {
+        const int64_t row = r0 + 16 * t + il;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const int c = kq + 4 * g;
+            if (row < n && c < bc) Out[row + (int64_t)c * ldo] = acc[t][g];
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void eigs_start_kernel(double* __restrict__ V, int64_t ldv, int64_t n, uint64_t seed) {
+    const int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int c = blockIdx.y;
+    if (row >= n) return;
+    uint64_t z = seed + ((uint64_t)row * 16u + (uint64_t)c + 1u) * 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    z ^= z >> 31;
+    V[row + (int64_t)c * ldv] = 2.0 * ((double)(z >> 11) * 0x1p-53) - 1.0;
+}
+
+hipError_t launch_eigs_gram(const double* V, int64_t ldv, int64_t vstride, int nb, const double* W, int64_t ldw,
+                            int64_t n, int b, double* part, double* out, hipStream_t st) {
+    if (n < 0 || nb < 0 || b < 0 || b > SOLVE_RHS || (n > 0 && (ldv < n || ldw < n))) return hipErrorInvalidValue;
+    if (nb == 0) return hipSuccess;
+    const bool rows = n > 0 && b > 0;
+    if (rows)
+        hipLaunchKernelGGL(eigs_gram_kernel, dim3((unsigned)eigs_groups(n)), dim3(256), 0, st, V, ldv, vstride, nb, W,
+                           ldw, n, b, part);
+    hipLaunchKernelGGL(eigs_gram_final_kernel, dim3(nb), dim3(256), 0, st, part, rows ? eigs_groups(n) : (int64_t)0,
+                       nb, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_eigs_update(double* Out, int64_t ldo, double beta, const double* W, int64_t ldw, const double* V,
+                              int64_t ldv, int64_t vstride, int nb, const double* C, int64_t n, int b, int bc,
+                              hipStream_t st) {
+    if (n < 0 || nb < 0 || b < 0 || b > SOLVE_RHS || bc < 0 || bc > SOLVE_RHS || (n > 0 && (ldo < n || (nb > 0 && ldv < n) || (beta != 0.0 && ldw < n))))
+        return hipErrorInvalidValue;
+    if (n == 0 || bc == 0) return hipSuccess;
+    hipLaunchKernelGGL(eigs_update_kernel, dim3((unsigned)((n + 64 * EIGS_UT - 1) / (64 * EIGS_UT))), dim3(256), 0, st,
+                       Out, ldo, beta, W, ldw, V, ldv, vstride, nb, C, n, b, bc);
+    return hipGetLastError();
+}
+
+hipError_t launch_eigs_start(double* V, int64_t ldv, int64_t n, int b, uint64_t seed, hipStream_t st) {
+    if (n < 0 || b < 0 || b > SOLVE_RHS || ldv < n) return hipErrorInvalidValue;
+    if (n == 0 || b == 0) return hipSuccess;
+    hipLaunchKernelGGL(eigs_start_kernel, dim3((unsigned)((n + 255) / 256), b), dim3(256), 0, st, V, ldv, n, seed);
+    return hipGetLastError();
+}
+
 }  // namespace sc

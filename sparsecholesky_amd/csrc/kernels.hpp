@@ -386,6 +386,37 @@ hipError_t launch_pcg_update(double* X, int64_t ldx, double* R, int64_t ldr, con
 hipError_t launch_pcg_dir(double* P, int64_t ldp, const double* Z, int64_t ldz, int64_t n, int nrhs, uint32_t mask,
                           const PcgCoef& beta, bool first, double* pt, hipStream_t st);
 
+// ---- dense algebra on tall panels for the block Lanczos eigensolver (eigs.cpp) ----
+// A panel is n x b (b <= SOLVE_RHS) column-major with a leading dimension; a basis is nb panels
+// vstride doubles apart.  Rows >= n and columns >= b are neither read nor written; they count as
+// zeros.  A 16 x 16 matrix M sits column-major in EIGS_TILE doubles, M(a, c) at a + 16 c.  Both
+// kernels run on v_mfma_f64_16x16x4_f64 and sum in an order fixed by n and nb alone.  No atomics.
+constexpr int EIGS_ROWS = 1024;  // rows per workgroup of the Gram kernel
+constexpr int EIGS_TILE = SOLVE_RHS * SOLVE_RHS;
+inline int64_t eigs_groups(int64_t n) { return n > 0 ? (n + EIGS_ROWS - 1) / EIGS_ROWS : 1; }
+// out[i] = V_i^T W for i < nb (entries with a or c >= b: zero).  Workgroup g owns the rows
+// [EIGS_ROWS g, + EIGS_ROWS): it loads them of W once (consecutive lanes read consecutive rows of
+// a column; through LDS into the MFMA's B operand, kept in registers), streams the same rows of
+// V_0, V_1, .. past them the same way and leaves one partial tile per block in part
+// (eigs_groups(n) x nb tiles: wave v sums its rows 256 q + 64 v + [0, 64), q < 4, four per MFMA
+// in ascending order, then the four waves add in order).  A second pass adds the partials of a
+// tile in workgroup order.  A block's result does not depend on nb or on its place in the basis.
+// V may be W.
+hipError_t launch_eigs_gram(const double* V, int64_t ldv, int64_t vstride, int nb, const double* W, int64_t ldw,
+                            int64_t n, int b, double* part, double* out, hipStream_t st);
+// Out = beta W + sum_{i < nb} V_i C_i; Out and W are n x bc, the V_i n x b and the C_i b x bc (nb
+// tiles, device; entries with a >= b or c >= bc are not read).  A wave takes 16 rows per step (four steps in flight) with four MFMAs per V_i, as the
+// transposed product C_i^T V_i^T: the result's rows lie on consecutive lanes.  beta == 0: W is
+// not read (it may be null).  A wave reads all it needs of its rows -- of W and of every V_i --
+// into registers before it writes them, and no wave touches another's rows, so Out may be W,
+// any V_i, or both (the CholQR scaling W <- W inv(R) runs in place with nb = 1, V = W = Out).
+hipError_t launch_eigs_update(double* Out, int64_t ldo, double beta, const double* W, int64_t ldw, const double* V,
+                              int64_t ldv, int64_t vstride, int nb, const double* C, int64_t n, int b, int bc,
+                              hipStream_t st);
+// The library's start block: V(i, c) = 2 u - 1, u = (splitmix64(seed + (16 i + c + 1) golden) >> 11)
+// 2^-53, golden = 0x9E3779B97F4A7C15 (the generator's own increment): a function of seed, i and c
+hipError_t launch_eigs_start(double* V, int64_t ldv, int64_t n, int b, uint64_t seed, hipStream_t st);
+
 // Small fronts (m <= maxm <= 128): one workgroup per front, factored in registers
 // (4 x 4 tiles per thread); seq: one workgroup runs the fronts in order (a whole
 // small tree in postorder, CBs through HBM).

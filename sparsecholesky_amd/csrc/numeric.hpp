@@ -414,6 +414,16 @@ struct Numeric {
     double* d_pcgpart = nullptr;
     double* d_pcgscal = nullptr;
 
+    // block Lanczos eigensolver (eigs.cpp; single-device handles), besides the product's buffers:
+    // the basis of eigs_blocks + 1 panels (n x SOLVE_RHS, ld = n), the Gram partials
+    // (eigs_groups(n) x eigs_blocks tiles), the coefficient buffer (2 eigs_blocks tiles) -- all
+    // three replaced by larger ones when a call asks for more blocks -- and the residual panel
+    int32_t eigs_blocks = 0;
+    double* d_egV = nullptr;
+    double* d_egpart = nullptr;
+    double* d_egC = nullptr;
+    double* d_egY = nullptr;
+
     std::string err;
 };
 
@@ -542,6 +552,22 @@ int64_t numeric_solve_pcg(Numeric& N, const sc_pcg_options& opt, int32_t nrhs, c
 int64_t debug_pcg_vec(int32_t which, int32_t n, int32_t nrhs, uint32_t mask, const double* coef, double* dA,
                       int64_t lda, double* dB, int64_t ldb, const double* dC, int64_t ldc, const double* dD, int64_t ldd,
                       double* dT, double* out, std::string& err);
+// The nev eigenpairs of the factored matrix nearest zero by block shift-invert Lanczos (eigs.cpp,
+// DESIGN.md section 9.7); values and status rules as numeric_solve_refine.  opt and the
+// arguments: validated by the caller.  lambda and info are host arrays in both forms.
+int64_t numeric_eigs(Numeric& N, const sc_eigs_options& opt, int32_t nev, const double* Ax, const double* X0,
+                     int64_t ldx0, double* lambda, double* X, int64_t ldx, sc_eigs_info* info, bool host,
+                     const char* who);
+// eigs.cpp's host dense algebra (include/sparsecholesky_debug.h: sc_debug_eigs_dense)
+bool eigs_sym_eig(int m, double* a, double* d);
+int eigs_chol_inv(const double* G, int b, double thr, double* rinv);
+// The Gram and the block-update kernel alone on caller panels (device), synchronous;
+// include/sparsecholesky_debug.h has the contracts.
+int64_t debug_eigs_gram(int32_t n, int32_t b, int32_t nb, const double* dV, int64_t ldv, int64_t vstride,
+                        const double* dW, int64_t ldw, double* out, std::string& err);
+int64_t debug_eigs_update(int32_t n, int32_t b, int32_t bc, int32_t nb, double beta, double* dOut, int64_t ldo,
+                          const double* dW, int64_t ldw, const double* dV, int64_t ldv, int64_t vstride,
+                          const double* C, std::string& err);
 // The kernels alone on a caller's structure (host arrays, validated: rp ascending from 0, ci
 // in [0, n), sp in [0, nval)) and values and panels (device pointers), synchronous: mode
 // SpmvMode; X, B, R, W column-major n x nrhs (nrhs <= SOLVE_RHS); W and norms (SPMV_NQ x
