@@ -34,7 +34,7 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define SC_VERSION 121 /* still 1.2.1, additive: eigenpairs nearest zero by block shift-invert Lanczos sc_eigs_host / sc_eigs_device / sc_default_eigs_options; still 1.2.1, additive: conjugate gradients preconditioned with the factor sc_solve_pcg_*_multi / sc_default_pcg_options; still 1.2.1, additive: products with A, residuals and iterative refinement sc_spmv_structure / sc_spmv_*_multi / sc_residual_*_multi / sc_solve_refine_*_multi / sc_default_refine_options; still 1.2.1, additive: Schur complement sc_analyze_schur / sc_symbolic_schur / sc_schur_factor_* / sc_schur_matrix_* / sc_schur_condense_*_multi / sc_schur_expand_*_multi; still 1.2.1, additive: rank-k update / downdate sc_updown_check / sc_updown_host; still 1.2.1, additive: selected inversion sc_selinv / sc_selinv_diag_host / sc_selinv_diag_device / sc_selinv_export / sc_selinv_flops; still 1.2.1, additive: the factor operators sc_apply_host / sc_apply_device / sc_apply_host_multi / sc_apply_device_multi (enum sc_factor_op) and sc_logdet; still 1.2.1, additive: sc_solve_host_multi / sc_solve_device_multi (nrhs right-hand sides); 1.2.1:small merged fronts amalgamated past relax_wmax (different supernode partition of some inputs, same L); 1.2.0: persistent slab chain options removed; panel_prefactor, dist_local_pieces and SC_ORDER_AMD added; out-of-range lookahead / inner_order / ordering rejected */
+#define SC_VERSION 121 /* still 1.2.1, additive: gradients of logdet and solve on A's pattern sc_value_entries / sc_pattern_outer_host / sc_pattern_outer_device / sc_pattern_dot_host / sc_pattern_dot_device / sc_logdet_grad_host / sc_logdet_grad_device / sc_solve_grad_host / sc_solve_grad_device; still 1.2.1, additive: eigenpairs nearest zero by block shift-invert Lanczos sc_eigs_host / sc_eigs_device / sc_default_eigs_options; still 1.2.1, additive: conjugate gradients preconditioned with the factor sc_solve_pcg_*_multi / sc_default_pcg_options; still 1.2.1, additive: products with A, residuals and iterative refinement sc_spmv_structure / sc_spmv_*_multi / sc_residual_*_multi / sc_solve_refine_*_multi / sc_default_refine_options; still 1.2.1, additive: Schur complement sc_analyze_schur / sc_symbolic_schur / sc_schur_factor_* / sc_schur_matrix_* / sc_schur_condense_*_multi / sc_schur_expand_*_multi; still 1.2.1, additive: rank-k update / downdate sc_updown_check / sc_updown_host; still 1.2.1, additive: selected inversion sc_selinv / sc_selinv_diag_host / sc_selinv_diag_device / sc_selinv_export / sc_selinv_flops; still 1.2.1, additive: the factor operators sc_apply_host / sc_apply_device / sc_apply_host_multi / sc_apply_device_multi (enum sc_factor_op) and sc_logdet; still 1.2.1, additive: sc_solve_host_multi / sc_solve_device_multi (nrhs right-hand sides); 1.2.1:small merged fronts amalgamated past relax_wmax (different supernode partition of some inputs, same L); 1.2.0: persistent slab chain options removed; panel_prefactor, dist_local_pieces and SC_ORDER_AMD added; out-of-range lookahead / inner_order / ordering rejected */
 
 enum sc_status {
     SC_OK = 0,
@@ -748,6 +748,70 @@ int64_t sc_eigs_host(sc_numeric* num, const sc_eigs_options* opt, int32_t nev, c
                      int64_t ldx0, double* lambda, double* X, int64_t ldx, sc_eigs_info* info);
 int64_t sc_eigs_device(sc_numeric* num, const sc_eigs_options* opt, int32_t nev, const double* d_Ax,
                        const double* d_X0, int64_t ldx0, double* lambda, double* d_X, int64_t ldx, sc_eigs_info* info);
+
+/* ---------------- gradients on A's pattern (single device) ----------------
+ * The derivatives of log det A and of X = inv(A) B with respect to the stored values of A, as
+ * sparse arrays of the length and order of the value array sc_factor takes.  Definitions, which
+ * every entry point below follows:
+ *   - An effective entry is a value slot k that the analysis uses: its row i_k is <= its column
+ *     j_k, and of several duplicates of one (row, column) it is the last.  These are exactly the
+ *     slots sc_spmv_structure's sp names.
+ *   - Every other slot is ignored; its derivative is zero.
+ *   - Every gradient array G has the length and order of Ai.
+ *   - Ignored slots of an output are written +0.0.
+ *   - Numbering is A's own, whatever the ordering or the Schur set of the handle.
+ * A stored entry stands for both mirrored positions, so with c_k = 1 on the diagonal and 2 off it
+ *     d logdet A / d a_k = c_k inv(A)[i_k, j_k],
+ * and for X = inv(A) B with an upstream Xbar: Bbar = inv(A) Xbar and
+ *     Abar_k = -sum_c (Bbar[i,c] X[j,c] + [i != j] Bbar[j,c] X[i,c]).
+ *   sc_value_entries       host only, no device: per value slot its row, its column and 0 / 1
+ *                          (effective); any array may be NULL; returns the slot count
+ *   sc_pattern_outer_*     per effective entry G_k = beta G_k + alpha sum_c (U[i,c] V[j,c] +
+ *                          [i != j] U[j,c] V[i,c]); beta == 0 does not read G.  U, V: n x nrhs
+ *                          column-major, any nrhs >= 0, taken in panels of 16: within a panel the
+ *                          16 columns are added by halving (absent columns count as zero), the
+ *                          first panel applies beta, later panels add in order.  Needs no
+ *                          factorization: works right after sc_numeric_create, like sc_spmv_*_multi
+ *   sc_pattern_dot_*       *out (host) = sum over the effective entries of G_k H_k, in a fixed
+ *                          tree; with H = dA this is the directional derivative tr(inv(A) dA)
+ *   sc_logdet_grad_*       G_k = c_k inv(A)[i_k, j_k], gathered from the Z panel of the selected
+ *                          inversion, which is computed first when it does not belong to the
+ *                          current factorization (the rules of sc_selinv_diag_*); after
+ *                          sc_updown_host it belongs to the updated matrix
+ *   sc_solve_grad_*        Bbar = the panel solve of Xbar, bit for bit what sc_solve_*_multi
+ *                          returns (Bbar may be Xbar when ldbb == ldxb), then G = the outer product
+ *                          with alpha = -1, beta = 0, U = Bbar, V = X
+ * No kernel uses atomics and every sum has an order fixed by n, the entry count and nrhs: results
+ * repeat bit for bit across calls and handles.
+ * Status: sc_logdet_grad_* and sc_solve_grad_* return SC_ERR_STATE before a factorization, and a
+ * failed factorization's status > 0, writing nothing; nrhs == 0 and n == 0 are legal; multi-rank
+ * and emulated handles SC_ERR_NOTIMPL with a message.  SC_ERR_ARG with the entry point's name in
+ * sc_last_error for a null handle, a null array (U, V, Xbar, X, Bbar with nrhs > 0 and n > 0; G,
+ * H with a non-empty value array; out), nrhs < 0, a leading dimension below n, G equal to U or V
+ * (sc_solve_grad_*: to Xbar, X or Bbar, or Bbar equal to X).  Calls are synchronous on the
+ * handle's stream.
+ * Device memory, counted in sc_numeric_memory info[0], allocated at the first of these calls and
+ * kept until sc_free_numeric, in bytes (ne = effective entries, ni = ignored slots, each list at
+ * least one element; n at least 1; nothing when n == 0 or the value array is empty):
+ *   16 ne                         the entry list (row, column, slot), in slot order
+ *   8 ni                          the ignored slots
+ *   2 x 128 n                     the 16-wide row-major copies of the U and the V panel
+ *   8 (ceil(ne / 1024) + 1)       the dot's partials and its result
+ * sc_logdet_grad_* also brings what sc_selinv lists, sc_solve_grad_* what the panel solve does;
+ * the host forms stage their arrays on the device for the length of the call. */
+int64_t sc_value_entries(const sc_symbolic* sym, int32_t* row, int32_t* col, int32_t* effective);
+int64_t sc_pattern_outer_host(sc_numeric* num, double alpha, int32_t nrhs, const double* U, int64_t ldu,
+                              const double* V, int64_t ldv, double beta, double* G);
+int64_t sc_pattern_outer_device(sc_numeric* num, double alpha, int32_t nrhs, const double* d_U, int64_t ldu,
+                                const double* d_V, int64_t ldv, double beta, double* d_G);
+int64_t sc_pattern_dot_host(sc_numeric* num, const double* G, const double* H, double* out);
+int64_t sc_pattern_dot_device(sc_numeric* num, const double* d_G, const double* d_H, double* out);
+int64_t sc_logdet_grad_host(sc_numeric* num, double* G);
+int64_t sc_logdet_grad_device(sc_numeric* num, double* d_G);
+int64_t sc_solve_grad_host(sc_numeric* num, int32_t nrhs, const double* Xbar, int64_t ldxb, const double* X,
+                           int64_t ldx, double* Bbar, int64_t ldbb, double* G);
+int64_t sc_solve_grad_device(sc_numeric* num, int32_t nrhs, const double* d_Xbar, int64_t ldxb, const double* d_X,
+                             int64_t ldx, double* d_Bbar, int64_t ldbb, double* d_G);
 
 /* ---------------- reference-API helpers (host) ----------------
  * Each mirrors one reference function, with int64 column pointers. */

@@ -209,6 +209,15 @@ _SIGS = [
     ("sc_default_eigs_options", None, [C.POINTER(EigsOptions)]),
     ("sc_eigs_host", _I64, [_P, C.POINTER(EigsOptions), _I32, _P, _P, _I64, _P, _P, _I64, _P]),
     ("sc_eigs_device", _I64, [_P, C.POINTER(EigsOptions), _I32, _P, _P, _I64, _P, _P, _I64, _P]),
+    ("sc_value_entries", _I64, [_P, _P, _P, _P]),
+    ("sc_pattern_outer_host", _I64, [_P, _D, _I32, _P, _I64, _P, _I64, _D, _P]),
+    ("sc_pattern_outer_device", _I64, [_P, _D, _I32, _P, _I64, _P, _I64, _D, _P]),
+    ("sc_pattern_dot_host", _I64, [_P, _P, _P, C.POINTER(_D)]),
+    ("sc_pattern_dot_device", _I64, [_P, _P, _P, C.POINTER(_D)]),
+    ("sc_logdet_grad_host", _I64, [_P, _P]),
+    ("sc_logdet_grad_device", _I64, [_P, _P]),
+    ("sc_solve_grad_host", _I64, [_P, _I32, _P, _I64, _P, _I64, _P, _I64, _P]),
+    ("sc_solve_grad_device", _I64, [_P, _I32, _P, _I64, _P, _I64, _P, _I64, _P]),
     ("sc_etree", _I64, [_I64, _P, _P, _P]),
     ("sc_post_order", _I64, [_I64, _P, _P]),
     ("sc_col_count", _I64, [_I64, _P, _P, _P, _P, _P]),
@@ -620,6 +629,18 @@ class Symbolic:
         sp = np.zeros(max(nz, 1), dtype=np.int64)
         assert _check(lib().sc_spmv_structure(self.h, _ptr(rp), _ptr(ci), _ptr(sp)), "spmv_structure") == nz
         return rp, ci[:nz], sp[:nz]
+
+    def value_entries(self) -> tuple:
+        """(rows, cols, effective), one entry per slot of the value array: the slot's row and
+        column as given, and whether the analysis uses it (row <= column, of duplicates the
+        last one -- the slots :meth:`spmv_structure`'s sp names).  Gradients are zero on the
+        other slots (sc_value_entries).  Host only."""
+        nnz = _check(lib().sc_value_entries(self.h, None, None, None), "value_entries")
+        rows = np.zeros(max(nnz, 1), dtype=np.int32)
+        cols = np.zeros(max(nnz, 1), dtype=np.int32)
+        eff = np.zeros(max(nnz, 1), dtype=np.int32)
+        assert _check(lib().sc_value_entries(self.h, _ptr(rows), _ptr(cols), _ptr(eff)), "value_entries") == nnz
+        return rows[:nnz], cols[:nnz], eff[:nnz].astype(bool)
 
     def stats(self) -> dict:
         st = SymbolicStats()
@@ -1305,6 +1326,109 @@ class Numeric:
             raise LibraryError(f"eigsh_device: A is not positive definite (column {st})")
         X = Xt.t()
         return (lam, X, self._eigs_info(info, nev)) if return_info else (lam, X)
+
+    def _nvalues(self) -> int:
+        return int(self.symb.A.p[self.symb.n]) if self.symb.n > 0 else 0
+
+    def _value_array(self, G, what: str) -> np.ndarray:
+        G = np.ascontiguousarray(G, dtype=np.float64)
+        if G.shape != (self._nvalues(),):
+            raise ValueError(f"{what}: the array is {G.shape}, the value array has {self._nvalues()} entries")
+        return G
+
+    def logdet_grad(self) -> np.ndarray:
+        """d logdet A / d values: per slot of the value array c inv(A)[i, j], c = 1 on the
+        diagonal and 2 off it (a stored entry stands for both mirrored positions), +0.0 on the
+        slots the analysis ignores (:meth:`Symbolic.value_entries`).  Gathered on the GPU from
+        the Z panel of :meth:`selinv`, which runs first when needed (sc_logdet_grad_host)."""
+        G = np.zeros(max(self._nvalues(), 1), dtype=np.float64)
+        st = _check(lib().sc_logdet_grad_host(self.h, _ptr(G)), "logdet_grad")
+        if st > 0:
+            raise LibraryError(f"logdet_grad: A is not positive definite (column {st})")
+        return G[:self._nvalues()]
+
+    def logdet_grad_device(self, d_G_ptr: int) -> int:
+        """:meth:`logdet_grad` into device memory of the value array's length at ``d_G_ptr``."""
+        st = _check(lib().sc_logdet_grad_device(self.h, C.c_void_p(d_G_ptr or None)), "logdet_grad_device")
+        if st > 0:
+            raise LibraryError(f"logdet_grad_device: A is not positive definite (column {st})")
+        return st
+
+    def pattern_outer(self, U: np.ndarray, V: np.ndarray, alpha: float = 1.0, beta: float = 0.0, G=None) -> np.ndarray:
+        """Per effective entry (i, j) of the value array: beta G + alpha sum_c (U[i, c] V[j, c]
+        + [i != j] U[j, c] V[i, c]), +0.0 on the ignored slots; U and V (n,) or (n, k).  With
+        ``beta == 0`` G is not read (and may be None).  Needs no factorization
+        (sc_pattern_outer_host)."""
+        Uf, _ = self._panel_in(U, "pattern_outer")
+        Vf, _ = self._panel_in(V, "pattern_outer")
+        if Uf.shape != Vf.shape:
+            raise ValueError(f"pattern_outer: U is {Uf.shape}, V {Vf.shape}")
+        if G is None:
+            if beta != 0.0:
+                raise ValueError("pattern_outer: beta != 0 needs G")
+            out = np.zeros(max(self._nvalues(), 1), dtype=np.float64)
+        else:
+            out = np.array(self._value_array(G, "pattern_outer"), copy=True)
+            if out.size == 0:
+                out = np.zeros(1, dtype=np.float64)
+        n, k = Uf.shape
+        ld = max(n, 1)
+        _check(lib().sc_pattern_outer_host(self.h, alpha, k, _ptr(Uf), ld, _ptr(Vf), ld, beta, _ptr(out)),
+               "pattern_outer")
+        return out[:self._nvalues()]
+
+    def pattern_outer_device(self, d_U_ptr: int, d_V_ptr: int, nrhs: int, ldu: int, ldv: int, d_G_ptr: int,
+                             alpha: float = 1.0, beta: float = 0.0) -> int:
+        """:meth:`pattern_outer` with device arrays, column-major as for :meth:`solve_device_multi`."""
+        return _check(lib().sc_pattern_outer_device(self.h, alpha, nrhs, C.c_void_p(d_U_ptr or None), ldu,
+                                                    C.c_void_p(d_V_ptr or None), ldv, beta,
+                                                    C.c_void_p(d_G_ptr or None)), "pattern_outer_device")
+
+    def pattern_dot(self, G: np.ndarray, H: np.ndarray) -> float:
+        """sum of G[k] H[k] over the effective entries, on the GPU in a fixed tree; with
+        G = :meth:`logdet_grad` and H = dA the directional derivative tr(inv(A) dA)
+        (sc_pattern_dot_host)."""
+        Gf, Hf = self._value_array(G, "pattern_dot"), self._value_array(H, "pattern_dot")
+        out = _D(0.0)
+        _check(lib().sc_pattern_dot_host(self.h, _ptr(Gf) if Gf.size else None, _ptr(Hf) if Hf.size else None,
+                                         C.byref(out)), "pattern_dot")
+        return out.value
+
+    def pattern_dot_device(self, d_G_ptr: int, d_H_ptr: int) -> float:
+        """:meth:`pattern_dot` with device arrays; the result comes back to the host."""
+        out = _D(0.0)
+        _check(lib().sc_pattern_dot_device(self.h, C.c_void_p(d_G_ptr or None), C.c_void_p(d_H_ptr or None),
+                                           C.byref(out)), "pattern_dot_device")
+        return out.value
+
+    def solve_grad(self, Xbar: np.ndarray, X: np.ndarray) -> tuple:
+        """(Bbar, G) for X = inv(A) B and an upstream gradient ``Xbar``: Bbar = inv(A) Xbar, the
+        gradient with respect to B (the panel solve, as :meth:`solve` of a 2-D array returns it),
+        and G = -:meth:`pattern_outer` (Bbar, X), the gradient with respect to the value array.
+        Xbar and X (n,) or (n, k); Bbar has their shape (sc_solve_grad_host)."""
+        Xb, one = self._panel_in(Xbar, "solve_grad")
+        Xf, _ = self._panel_in(X, "solve_grad")
+        if Xb.shape != Xf.shape:
+            raise ValueError(f"solve_grad: Xbar is {Xb.shape}, X {Xf.shape}")
+        n, k = Xb.shape
+        Bbar = np.zeros((n, k), dtype=np.float64, order="F")
+        G = np.zeros(max(self._nvalues(), 1), dtype=np.float64)
+        ld = max(n, 1)
+        st = _check(lib().sc_solve_grad_host(self.h, k, _ptr(Xb), ld, _ptr(Xf), ld, _ptr(Bbar), ld, _ptr(G)),
+                    "solve_grad")
+        if st > 0:
+            raise LibraryError(f"solve_grad: A is not positive definite (column {st})")
+        return (Bbar[:, 0] if one else Bbar), G[:self._nvalues()]
+
+    def solve_grad_device(self, d_Xbar_ptr: int, d_X_ptr: int, nrhs: int, ldxb: int, ldx: int, d_Bbar_ptr: int,
+                          ldbb: int, d_G_ptr: int) -> int:
+        """:meth:`solve_grad` with device arrays, column-major as for :meth:`solve_device_multi`."""
+        st = _check(lib().sc_solve_grad_device(self.h, nrhs, C.c_void_p(d_Xbar_ptr or None), ldxb,
+                                               C.c_void_p(d_X_ptr or None), ldx, C.c_void_p(d_Bbar_ptr or None), ldbb,
+                                               C.c_void_p(d_G_ptr or None)), "solve_grad_device")
+        if st > 0:
+            raise LibraryError(f"solve_grad_device: A is not positive definite (column {st})")
+        return st
 
     def selinv(self) -> int:
         """Selected inversion: every entry of A^-1 on the pattern of L into the handle's Z

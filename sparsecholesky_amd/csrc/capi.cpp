@@ -161,6 +161,8 @@ static int64_t analyze_impl(int64_t n, const int64_t* Ap, const int32_t* Ai, con
                 auto& S = h->S;
                 for (int64_t q = 0; q < S.nnzA_used; ++q) S.a_src[q] = src[S.a_src[q]];
                 S.nnzA_in = Ap[n];
+                S.Ap_in.assign(Ap, Ap + n + 1);
+                S.Ai_in.assign(Ai, Ai + Ap[n]);
                 S.perm = std::move(perm);
                 S.n_schur = ns;
             }
@@ -1043,6 +1045,126 @@ int64_t sc_eigs_host(sc_numeric* num, const sc_eigs_options* opt, int32_t nev, c
 int64_t sc_eigs_device(sc_numeric* num, const sc_eigs_options* opt, int32_t nev, const double* d_Ax, const double* d_X0,
                        int64_t ldx0, double* lambda, double* d_X, int64_t ldx, sc_eigs_info* info) {
     return eigs_entry(num, opt, nev, d_Ax, d_X0, ldx0, lambda, d_X, ldx, info, false, "sc_eigs_device");
+}
+
+// ---- gradients on A's pattern ----
+int64_t sc_value_entries(const sc_symbolic* sym, int32_t* row, int32_t* col, int32_t* effective) {
+    if (!sym) {
+        g_last_error = "sc_value_entries: null handle";
+        return SC_ERR_ARG;
+    }
+    return sc::value_entries(sym->S, row, col, effective);
+}
+
+// a value-length array may be null only when the value array is empty
+static int64_t grad_value_arg(sc_numeric* num, const void* a, const char* name, const char* who) {
+    if (a || num->N->S->nnzA_in == 0) return SC_OK;
+    g_last_error = std::string(who) + ": null " + name;
+    return SC_ERR_ARG;
+}
+
+static int64_t grad_finish(sc_numeric* num, int64_t rc) {
+    if (rc < 0) g_last_error = num->N->err;
+    return rc;
+}
+
+static int64_t pattern_outer(sc_numeric* num, double alpha, int32_t nrhs, const double* U, int64_t ldu, const double* V,
+                             int64_t ldv, double beta, double* G, bool host, const char* who) {
+    int64_t rc = panel_args(num, nrhs, {{U, ldu, "U"}, {V, ldv, "V"}}, who);
+    if (rc == SC_OK) rc = grad_value_arg(num, G, "G", who);
+    if (rc != SC_OK) return rc;
+    if (G && ((const double*)G == U || (const double*)G == V)) {
+        g_last_error = std::string(who) + ": G aliases U or V";
+        return SC_ERR_ARG;
+    }
+    try {
+        rc = sc::numeric_pattern_outer(*num->N, alpha, nrhs, U, ldu, V, ldv, beta, G, host, who);
+    } catch (const std::bad_alloc&) {
+        return SC_ERR_NOMEM;
+    }
+    return grad_finish(num, rc);
+}
+
+int64_t sc_pattern_outer_host(sc_numeric* num, double alpha, int32_t nrhs, const double* U, int64_t ldu,
+                              const double* V, int64_t ldv, double beta, double* G) {
+    return pattern_outer(num, alpha, nrhs, U, ldu, V, ldv, beta, G, true, "sc_pattern_outer_host");
+}
+int64_t sc_pattern_outer_device(sc_numeric* num, double alpha, int32_t nrhs, const double* d_U, int64_t ldu,
+                                const double* d_V, int64_t ldv, double beta, double* d_G) {
+    return pattern_outer(num, alpha, nrhs, d_U, ldu, d_V, ldv, beta, d_G, false, "sc_pattern_outer_device");
+}
+
+static int64_t pattern_dot(sc_numeric* num, const double* G, const double* H, double* out, bool host, const char* who) {
+    if (!num || !num->N || !out) {
+        g_last_error = std::string(who) + ((!num || !num->N) ? ": null handle" : ": null out");
+        return SC_ERR_ARG;
+    }
+    int64_t rc = grad_value_arg(num, G, "G", who);
+    if (rc == SC_OK) rc = grad_value_arg(num, H, "H", who);
+    if (rc != SC_OK) return rc;
+    try {
+        rc = sc::numeric_pattern_dot(*num->N, G, H, out, host, who);
+    } catch (const std::bad_alloc&) {
+        return SC_ERR_NOMEM;
+    }
+    return grad_finish(num, rc);
+}
+
+int64_t sc_pattern_dot_host(sc_numeric* num, const double* G, const double* H, double* out) {
+    return pattern_dot(num, G, H, out, true, "sc_pattern_dot_host");
+}
+int64_t sc_pattern_dot_device(sc_numeric* num, const double* d_G, const double* d_H, double* out) {
+    return pattern_dot(num, d_G, d_H, out, false, "sc_pattern_dot_device");
+}
+
+static int64_t logdet_grad(sc_numeric* num, double* G, bool host, const char* who) {
+    if (!num || !num->N) {
+        g_last_error = std::string(who) + ": null handle";
+        return SC_ERR_ARG;
+    }
+    int64_t rc = grad_value_arg(num, G, "G", who);
+    if (rc != SC_OK) return rc;
+    try {
+        rc = sc::numeric_logdet_grad(*num->N, G, host, who);
+    } catch (const std::bad_alloc&) {
+        return SC_ERR_NOMEM;
+    }
+    return grad_finish(num, rc);
+}
+
+int64_t sc_logdet_grad_host(sc_numeric* num, double* G) { return logdet_grad(num, G, true, "sc_logdet_grad_host"); }
+int64_t sc_logdet_grad_device(sc_numeric* num, double* d_G) {
+    return logdet_grad(num, d_G, false, "sc_logdet_grad_device");
+}
+
+static int64_t solve_grad(sc_numeric* num, int32_t nrhs, const double* Xbar, int64_t ldxb, const double* X, int64_t ldx,
+                          double* Bbar, int64_t ldbb, double* G, bool host, const char* who) {
+    int64_t rc = panel_args(num, nrhs, {{Xbar, ldxb, "Xbar"}, {X, ldx, "X"}, {Bbar, ldbb, "Bbar"}}, who);
+    if (rc == SC_OK) rc = grad_value_arg(num, G, "G", who);
+    if (rc != SC_OK) return rc;
+    if (G && ((const double*)G == Xbar || (const double*)G == X || G == Bbar)) {
+        g_last_error = std::string(who) + ": G aliases Xbar, X or Bbar";
+        return SC_ERR_ARG;
+    }
+    if (nrhs > 0 && num->N->S->n > 0 && (const double*)Bbar == X) {
+        g_last_error = std::string(who) + ": Bbar aliases X";
+        return SC_ERR_ARG;
+    }
+    try {
+        rc = sc::numeric_solve_grad(*num->N, nrhs, Xbar, ldxb, X, ldx, Bbar, ldbb, G, host, who);
+    } catch (const std::bad_alloc&) {
+        return SC_ERR_NOMEM;
+    }
+    return grad_finish(num, rc);
+}
+
+int64_t sc_solve_grad_host(sc_numeric* num, int32_t nrhs, const double* Xbar, int64_t ldxb, const double* X,
+                           int64_t ldx, double* Bbar, int64_t ldbb, double* G) {
+    return solve_grad(num, nrhs, Xbar, ldxb, X, ldx, Bbar, ldbb, G, true, "sc_solve_grad_host");
+}
+int64_t sc_solve_grad_device(sc_numeric* num, int32_t nrhs, const double* d_Xbar, int64_t ldxb, const double* d_X,
+                             int64_t ldx, double* d_Bbar, int64_t ldbb, double* d_G) {
+    return solve_grad(num, nrhs, d_Xbar, ldxb, d_X, ldx, d_Bbar, ldbb, d_G, false, "sc_solve_grad_device");
 }
 
 int64_t sc_debug_eigs_gram(int32_t n, int32_t b, int32_t nb, const double* d_V, int64_t ldv, int64_t vstride,

@@ -4319,4 +4319,145 @@ hipError_t launch_eigs_start(double* V, int64_t ldv, int64_t n, int b, uint64_t 
     return hipGetLastError();
 }
 
+// ---- gradients on A's pattern (kernels.hpp has the contracts) ----
+__global__ __launch_bounds__(256) void grad_zero_slots_kernel(double* __restrict__ G, const int64_t* __restrict__ slot,
+                                                              int64_t count) {
+    const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (q < count) G[slot[q]] = 0.0;
+}
+
+// Sixteen lanes per entry, lane c its column c: a lane group reads one 128-byte row of ut and
+// one of vt (both pairs off the diagonal), and the group's lane 0 owns the entry's slot of G.
+template <bool FIRST>
+__global__ __launch_bounds__(256) void grad_outer_kernel(const GradEntry* __restrict__ ent, int64_t ne,
+                                                         const double* __restrict__ ut, const double* __restrict__ vt,
+                                                         int nrhs, double alpha, double beta, double* __restrict__ G) {
+    const int tid = threadIdx.x, c = tid & 15, g = tid >> 4;
+    const int64_t e0 = (int64_t)blockIdx.x * GRAD_EPW + g;
+#pragma unroll 4
+    for (int q = 0; q < GRAD_EPW / 16; ++q) {
+        const int64_t e = e0 + 16 * q;
+        const bool on = e < ne;  // uniform over the lane group
+        double t = 0.0;
+        int64_t slot = 0;
+        if (on) {
+            const GradEntry en = ent[e];
+            slot = en.slot;
+            if (c < nrhs) {
+                const int64_t i = (int64_t)en.row * SOLVE_RHS + c, j = (int64_t)en.col * SOLVE_RHS + c;
+                t = ut[i] * vt[j];
+                if (en.row != en.col) t = fma(ut[j], vt[i], t);
+            }
+        }
+        // every lane of the wave takes part in the exchange; a group's lanes all end with its sum
+        t += __shfl_xor(t, 8, 16);
+        t += __shfl_xor(t, 4, 16);
+        t += __shfl_xor(t, 2, 16);
+        t += __shfl_xor(t, 1, 16);
+        if (on && c == 0) {
+            if (FIRST)
+                G[slot] = fma(alpha, t, beta == 0.0 ? 0.0 : beta * G[slot]);
+            else
+                G[slot] = fma(alpha, t, G[slot]);
+        }
+    }
+}
+
+__global__ __launch_bounds__(LOGDET_NT) void grad_zgather_kernel(SelPlan P, int ns, int n,
+                                                                 const int64_t* __restrict__ a_ptr,
+                                                                 const int32_t* __restrict__ a_pos,
+                                                                 const int64_t* __restrict__ a_src,
+                                                                 double* __restrict__ G) {
+    const int j = (int)blockIdx.x * LOGDET_NT + (int)threadIdx.x;
+    if (j >= n) return;
+    int lo = 0, hi = ns;  // sn_start[lo] <= j < sn_start[hi]
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (P.sn_start[mid] <= j)
+            lo = mid;
+        else
+            hi = mid;
+    }
+    const int jl = j - P.sn_start[lo];
+    const double* z = P.zpanel + P.panel_off[lo] + (int64_t)jl * P.sn_m[lo];
+    for (int64_t q = a_ptr[j]; q < a_ptr[j + 1]; ++q) {
+        const int p = a_pos[q];  // jl <= p < m: the lower position, valid in the mirrored pivot square too
+        const double v = z[p];
+        G[a_src[q]] = p == jl ? v : 2.0 * v;
+    }
+}
+
+__global__ __launch_bounds__(256) void grad_dot_kernel(const GradEntry* __restrict__ ent, int64_t ne,
+                                                       const double* __restrict__ G, const double* __restrict__ H,
+                                                       double* __restrict__ part) {
+    __shared__ double red[4];
+    const int tid = threadIdx.x;
+    const int64_t e0 = (int64_t)blockIdx.x * GRAD_ROWS + tid;
+    double s = 0.0;
+#pragma unroll
+    for (int k = 0; k < GRAD_ROWS / 256; ++k) {
+        const int64_t e = e0 + 256 * k;
+        if (e < ne) {
+            const int64_t slot = ent[e].slot;
+            s = fma(G[slot], H[slot], s);
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o);
+    if ((tid & 63) == 0) red[tid >> 6] = s;
+    __syncthreads();
+    if (tid == 0) part[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+__global__ __launch_bounds__(256) void grad_dot_final_kernel(const double* __restrict__ part, int64_t nslots,
+                                                             double* __restrict__ out) {
+    __shared__ double red[256];
+    const int tid = threadIdx.x;
+    double v = 0.0;
+    for (int64_t s = tid; s < nslots; s += 256) v += part[s];
+    red[tid] = v;
+    __syncthreads();
+    for (int h = 128; h > 0; h >>= 1) {
+        if (tid < h) red[tid] += red[tid + h];
+        __syncthreads();
+    }
+    if (tid == 0) out[0] = red[0];
+}
+
+hipError_t launch_grad_zero_slots(double* G, const int64_t* slot, int64_t count, hipStream_t st) {
+    if (count <= 0) return hipSuccess;
+    hipLaunchKernelGGL(grad_zero_slots_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st, G, slot, count);
+    return hipGetLastError();
+}
+
+hipError_t launch_grad_outer(const GradEntry* ent, int64_t ne, const double* ut, const double* vt, int nrhs,
+                             double alpha, double beta, bool first, double* G, hipStream_t st) {
+    if (nrhs < 0 || nrhs > SOLVE_RHS || ne < 0) return hipErrorInvalidValue;
+    if (ne == 0) return hipSuccess;
+    const dim3 grid((unsigned)((ne + GRAD_EPW - 1) / GRAD_EPW));
+    if (first)
+        hipLaunchKernelGGL(grad_outer_kernel<true>, grid, dim3(256), 0, st, ent, ne, ut, vt, nrhs, alpha, beta, G);
+    else
+        hipLaunchKernelGGL(grad_outer_kernel<false>, grid, dim3(256), 0, st, ent, ne, ut, vt, nrhs, alpha, beta, G);
+    return hipGetLastError();
+}
+
+hipError_t launch_grad_zgather(const SelPlan& P, int ns, int64_t n, const int64_t* a_ptr, const int32_t* a_pos,
+                               const int64_t* a_src, double* G, hipStream_t st) {
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(grad_zgather_kernel, dim3((unsigned)((n + LOGDET_NT - 1) / LOGDET_NT)), dim3(LOGDET_NT), 0, st,
+                       P, ns, (int)n, a_ptr, a_pos, a_src, G);
+    return hipGetLastError();
+}
+
+hipError_t launch_grad_dot(const GradEntry* ent, int64_t ne, const double* G, const double* H, double* part,
+                           double* out, hipStream_t st) {
+    if (ne < 0) return hipErrorInvalidValue;
+    if (ne > 0)
+        hipLaunchKernelGGL(grad_dot_kernel, dim3((unsigned)grad_dot_groups(ne)), dim3(256), 0, st, ent, ne, G, H, part);
+    hipLaunchKernelGGL(grad_dot_final_kernel, dim3(1), dim3(256), 0, st, part, ne > 0 ? grad_dot_groups(ne) : (int64_t)0,
+                       out);
+    return hipGetLastError();
+}
+
 }  // namespace sc

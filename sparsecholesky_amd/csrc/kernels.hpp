@@ -417,6 +417,39 @@ hipError_t launch_eigs_update(double* Out, int64_t ldo, double beta, const doubl
 // 2^-53, golden = 0x9E3779B97F4A7C15 (the generator's own increment): a function of seed, i and c
 hipError_t launch_eigs_start(double* V, int64_t ldv, int64_t n, int b, uint64_t seed, hipStream_t st);
 
+// ---- gradients on A's pattern (grad.cpp) ----
+// An effective entry of A: a value slot the analysis uses, row <= col in A's own numbering.
+// The list is in ascending slot order, so a pass writes G in runs.
+struct GradEntry {
+    int32_t row, col;
+    int64_t slot;
+};
+constexpr int GRAD_EPW = 256;    // entries per workgroup of the outer pass (16 at a time, one per 16 lanes)
+constexpr int GRAD_ROWS = 1024;  // entries per workgroup of the dot pass
+inline int64_t grad_dot_groups(int64_t ne) { return ne > 0 ? (ne + GRAD_ROWS - 1) / GRAD_ROWS : 1; }
+// G[slot[q]] = +0.0 for q < count (the ignored slots of an output)
+hipError_t launch_grad_zero_slots(double* G, const int64_t* slot, int64_t count, hipStream_t st);
+// Sampled outer product of one panel of nrhs <= SOLVE_RHS columns, U and V in the 16-wide
+// row-major form of launch_spmv_transpose.  Per entry (i, j, k), s = sum_c (ut[i, c] vt[j, c]
+// + [i != j] ut[j, c] vt[i, c]): the products of a column by one multiply and one fma, the 16
+// columns by halving (8, 4, 2, 1; columns >= nrhs count as zero and are not loaded).  first:
+// G[k] = fma(alpha, s, beta G[k]), with beta == 0 G is not read; else G[k] = fma(alpha, s,
+// G[k]).  Sixteen lanes per entry; nothing but the ne listed slots of G is touched.
+hipError_t launch_grad_outer(const GradEntry* ent, int64_t ne, const double* ut, const double* vt, int nrhs,
+                             double alpha, double beta, bool first, double* G, hipStream_t st);
+// The assembly's A-entry map backwards over the Z panel of the selected inversion: for the
+// entries q of internal column j (local column jl of supernode s, m front rows), G[a_src[q]] =
+// c zpanel[panel_off[s] + jl m + a_pos[q]], c = 1 at the pivot row (a_pos[q] == jl), else 2.
+// One thread per column; a_src is injective, so no slot has two writers.
+hipError_t launch_grad_zgather(const SelPlan& P, int ns, int64_t n, const int64_t* a_ptr, const int32_t* a_pos,
+                               const int64_t* a_src, double* G, hipStream_t st);
+// out[0] = sum over the ne entries of G[slot] H[slot], in a fixed tree: a lane's GRAD_ROWS / 256
+// entries (stride 256) by fma, the 64 lanes of a wave by halving, the four waves in order, one
+// partial per workgroup (part: grad_dot_groups(ne) doubles); then one workgroup adds partial s
+// on lane s % 256 in ascending order and the 256 lane sums by halving.  No atomics.
+hipError_t launch_grad_dot(const GradEntry* ent, int64_t ne, const double* G, const double* H, double* part,
+                           double* out, hipStream_t st);
+
 // Small fronts (m <= maxm <= 128): one workgroup per front, factored in registers
 // (4 x 4 tiles per thread); seq: one workgroup runs the fronts in order (a whole
 // small tree in postorder, CBs through HBM).

@@ -424,6 +424,18 @@ struct Numeric {
     double* d_egC = nullptr;
     double* d_egY = nullptr;
 
+    // gradients on A's pattern (grad.cpp; single-device handles): the effective entries (row,
+    // column, slot) in slot order, the ignored slots, the two transposed panels of the outer
+    // product (SOLVE_RHS-wide rows) and the dot's partials with its result behind them,
+    // allocated at the first use, kept
+    bool grad_ready = false;
+    GradEntry* d_gent = nullptr;
+    int64_t* d_gign = nullptr;
+    int64_t grad_ne = 0, grad_nign = 0;
+    double* d_gut = nullptr;
+    double* d_gvt = nullptr;
+    double* d_gpart = nullptr;
+
     std::string err;
 };
 
@@ -558,6 +570,24 @@ int64_t debug_pcg_vec(int32_t which, int32_t n, int32_t nrhs, uint32_t mask, con
 int64_t numeric_eigs(Numeric& N, const sc_eigs_options& opt, int32_t nev, const double* Ax, const double* X0,
                      int64_t ldx0, double* lambda, double* X, int64_t ldx, sc_eigs_info* info, bool host,
                      const char* who);
+// Gradients on A's pattern (grad.cpp).  G, H: arrays of the length and
+// order of the analysed pattern's values; an effective entry is a slot the analysis uses (the
+// set of spmv_structure's sp), every other slot of an output is written +0.0.  U, V, X, Xbar,
+// Bbar: n x nrhs column-major in A's own order.  Device or host memory by `host`; synchronous
+// on the handle's stream; multi-rank and emulated handles SC_ERR_NOTIMPL.  Arguments are
+// validated by the caller.
+//   pattern_outer  G_k = beta G_k + alpha sum_c (U[i,c] V[j,c] + [i != j] U[j,c] V[i,c]); never
+//                  looks at the factor
+//   pattern_dot    *out (host) = sum over the effective entries of G_k H_k
+//   logdet_grad    G_k = c_k inv(A)[i_k, j_k] from the Z panel (computed first when it does
+//                  not belong to the current factorization); status rules of the selected inversion
+//   solve_grad     Bbar = the panel solve of Xbar, G = pattern_outer(-1, Bbar, X, 0)
+int64_t numeric_pattern_outer(Numeric& N, double alpha, int32_t nrhs, const double* U, int64_t ldu, const double* V,
+                              int64_t ldv, double beta, double* G, bool host, const char* who);
+int64_t numeric_pattern_dot(Numeric& N, const double* G, const double* H, double* out, bool host, const char* who);
+int64_t numeric_logdet_grad(Numeric& N, double* G, bool host, const char* who);
+int64_t numeric_solve_grad(Numeric& N, int32_t nrhs, const double* Xbar, int64_t ldxb, const double* X, int64_t ldx,
+                           double* Bbar, int64_t ldbb, double* G, bool host, const char* who);
 // eigs.cpp's host dense algebra (include/sparsecholesky_debug.h: sc_debug_eigs_dense)
 bool eigs_sym_eig(int m, double* a, double* d);
 int eigs_chol_inv(const double* G, int b, double thr, double* rinv);

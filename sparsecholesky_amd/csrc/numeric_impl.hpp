@@ -118,6 +118,10 @@ struct SolveCut {
 };
 void solve_cut_front(int32_t s, int w, int m, int k0, int64_t goff, SolveCut& C);
 
+// selinv.cpp: the Z panel of the current factorization, computed if it is not there (the
+// status rules of numeric_selinv)
+int64_t selinv_ensure(Numeric& N);
+
 // refine.cpp: what the products with A, the refinement and the conjugate gradients share
 // a device buffer for the length of one host call
 struct DevTemp {

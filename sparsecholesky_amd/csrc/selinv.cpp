@@ -192,7 +192,7 @@ int64_t numeric_selinv(Numeric& N) {
 }
 
 // the Z panel of the current factorization, computed if it is not there
-static int64_t selinv_ensure(Numeric& N) {
+int64_t selinv_ensure(Numeric& N) {
     if (N.factored && N.sel_gen == N.factor_gen && N.sel_ready) return numeric_status(N);
     return numeric_selinv(N);
 }

@@ -72,4 +72,20 @@ i64 spmv_structure(const Symbolic& S, i64* rp, i32* ci, i64* sp) {
     return total;
 }
 
+i64 value_entries(const Symbolic& S, i32* row, i32* col, i32* effective) {
+    const i64 n = S.n, nnz = S.nnzA_in;
+    const std::vector<i64>& Ap = S.Ap_in.empty() ? S.Ap : S.Ap_in;
+    const std::vector<i32>& Ai = S.Ap_in.empty() ? S.Ai : S.Ai_in;
+    for (i64 k = 0; k < n; ++k)
+        for (i64 p = Ap[k]; p < Ap[k + 1]; ++p) {
+            if (row) row[p] = Ai[p];
+            if (col) col[p] = (i32)k;
+        }
+    if (effective) {
+        std::fill(effective, effective + nnz, 0);
+        for (i64 q = 0; q < S.nnzA_used; ++q) effective[S.a_src[q]] = 1;
+    }
+    return nnz;
+}
+
 }  // namespace sc

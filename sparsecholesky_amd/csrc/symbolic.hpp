@@ -48,6 +48,10 @@ struct Symbolic {
     i64 nnzA_used = 0; // upper entries actually used
     std::vector<i64> Ap;  // copy of input pattern (natural)
     std::vector<i32> Ai;
+    // the caller's own pattern where Ap / Ai hold the permuted one (an ordering or a Schur
+    // set is in effect); empty: Ap / Ai are the caller's
+    std::vector<i64> Ap_in;
+    std::vector<i32> Ai_in;
 
     // natural-order symbolic (reference semantics)
     std::vector<i32> perm;      // fill-reducing ordering, new -> old (empty: the given order)
@@ -123,6 +127,10 @@ void permute_upper(i64 n, const i64* Ap, const i32* Ai, const i32* perm, std::ve
 // sp are given the ascending columns and the value indices into the caller's array.  Returns
 // the entry count.
 i64 spmv_structure(const Symbolic& S, i64* rp, i32* ci, i64* sp);
+// The caller's value slots one by one (spmv.cpp): row, column (as given, A's own numbering)
+// and whether the analysis uses the slot (row <= column, of duplicates the last one: exactly
+// the slots spmv_structure's sp names).  Any array may be null.  Returns the slot count.
+i64 value_entries(const Symbolic& S, i32* row, i32* col, i32* effective);
 
 // Reference-layout pattern of L (schol().p()/i()), natural numbering.
 void pattern_L(const Symbolic& S, i64* Lp, i32* Li);
