@@ -813,6 +813,141 @@ int64_t sc_solve_grad_host(sc_numeric* num, int32_t nrhs, const double* Xbar, in
 int64_t sc_solve_grad_device(sc_numeric* num, int32_t nrhs, const double* d_Xbar, int64_t ldxb, const double* d_X,
                              int64_t ldx, double* d_Bbar, int64_t ldbb, double* d_G);
 
+/* Weighted normal equations, formed and factored on the GPU.  For a
+ * rectangular sparse J (m x n, CSC), row weights w (m), an optional symmetric base matrix C
+ * (n x n, its upper triangle in CSC), an optional diagonal d (n) and a damping lambda,
+ *     S = C + J^T diag(w) J + diag(d) + lambda I:
+ * the normal equations of Newton and interior-point steps, Gauss-Newton and Levenberg-Marquardt,
+ * reweighted least squares, the posterior precision Q + A^T W A.  An sc_normal handle holds the
+ * structure only (it is independent of sc_symbolic and sc_numeric); the values J, w, C, d come
+ * with every call, so a new w or lambda per step costs one pass over the term lists.
+ *   sc_normal_create    validates and builds.  SC_ERR_ARG with a message in sc_last_error when
+ *                       J's row indices do not ascend strictly within a column or leave [0, m),
+ *                       J has more than 2^31 - 1 entries (a term holds 32-bit positions) or more
+ *                       than 2^40 terms, S would have more than 2^31 - 1 entries, or a base entry
+ *                       has row > column.  Cp == NULL: no base.
+ *                       No HIP call: the device side is built at the first call that needs it
+ *                       (device < 0: the device of the sc_numeric of the first factor call, else
+ *                       the current one).
+ *   sc_normal_pattern   the pattern of S -- upper triangle, CSC, rows ascending: every diagonal
+ *                       entry, every (i, j), i < j, whose J columns share a row, every entry of
+ *                       C -- in the form sc_analyze / sc_analyze_schur take.  Two-phase: returns
+ *                       the entry count; Sp (n + 1) and Si are filled when not NULL.
+ *   sc_normal_terms     T = sum over J's rows of nnz_r (nnz_r + 1) / 2, the terms of all entries.
+ *   sc_normal_term_lists  host copies for tests, two-phase (returns T): tp (entries + 1), per
+ *                       term the positions pa, pb of J[r, i] and J[r, j] in J's value array and
+ *                       the row r (rows ascend within an entry's list), per entry cpos, the
+ *                       position of its value in C's array or -1.
+ *   sc_normal_rows      J by rows, as sc_spmv_structure gives A: rp (m + 1), columns ci ascending,
+ *                       sp the position in J's value array.  Two-phase, returns nnz(J).
+ *   sc_normal_memory    out[0 .. 4): host bytes of the structure, device bytes held, T, entries
+ *                       of S; returns 4.
+ *   sc_normal_constants out[0 .. 4): the boundaries between the form kernel's mappings (lists of
+ *                       at most out[0] terms: one lane per entry; up to out[2]: out[1] lanes per
+ *                       entry; above: chunks of out[2] terms) and out[3], the entries per chunk of
+ *                       a long column or row of the products; returns 4.
+ * Values.  S_e = (c_e + [i = j] (d_i + lambda)) + sum_t (J[pa_t] w[r_t]) J[pb_t], every product
+ * rounded twice (J w, then the fma with the other J), in this order: a list of at most 8 terms
+ * is added to the base term by term in list order; a longer one is summed by 16 lanes -- lane l
+ * takes the terms l, l + 16, .. in order, starting from zero, and the 16 lane sums are added by
+ * halving (8, 4, 2, 1) -- and the base is added last; a list above 256 terms runs in chunks of
+ * 256, each summed as such a list, the partials added in chunk order, then the base.  No
+ * atomics: the values are bitwise repeatable across calls and handles.  Any order satisfies
+ *     |S_e - exact| <= gamma_(t + 3) (|c_e| + |d_i + lambda| + sum |J w J|),  t the list length.
+ *   sc_normal_values_*  the values into the caller's array (entries of S doubles, the order of
+ *                       Si: what sc_factor_device reads).  w (ones), Cx (zeros) and d (zeros) may
+ *                       be NULL.
+ *   sc_normal_factor_*  forms into a buffer the handle owns and calls sc_factor_device(num,
+ *                       buffer, 1); returns the factorization's status (> 0: the failing column
+ *                       + 1 in the factored order, as for any matrix that is not positive
+ *                       definite -- a rank-deficient J without damping ends there).  SC_ERR_ARG
+ *                       when num's analysis has another n or value count or lives on another
+ *                       device; multi-rank and emulated handles SC_ERR_NOTIMPL with a message.
+ *   sc_normal_values_ptr  that device buffer (NULL until an sc_normal_factor_* has filled it),
+ *                       valid until sc_normal_free, its contents until the next
+ *                       sc_normal_factor_* on the handle: pass it as
+ *                       d_Ax to sc_residual_*, sc_solve_refine_*, sc_solve_pcg_*, sc_solve_grad_*.
+ * Products, in panels of 16 columns, column-major with leading dimensions (checked against the
+ * row counts as in sc_spmv_*_multi; an output that is the input: SC_ERR_ARG):
+ *   sc_normal_mul_*_multi   Y (m x nrhs) = J X, one fma per entry along a row, columns ascending
+ *   sc_normal_mult_*_multi  G (n x nrhs) = J^T diag(w) Y, down J's columns: (J w) rounded, then
+ *                           one fma per entry; w may be NULL (ones)
+ * A row or column above 256 entries is summed in chunks of 256 whose partials are added in chunk
+ * order.  A column's bits do not depend on the columns it travels with.
+ * Device memory per handle, allocated at the first device call and kept until sc_normal_free:
+ *   12 T                       the term lists (three int32 per term)
+ *   20 ne + 24 tasks           per entry of S: list start, base position, diagonal column; a
+ *                              task = a list above 8 terms or one chunk of it
+ *   12 nnz(J) + 8 (n + 1)      J by columns;  20 nnz(J) + 8 (m + 1)  J by rows;  16 per task
+ *   8 ne                       the value buffer;  128 max(m, n)  the 16-wide right-hand panel
+ * plus the partial slots of chunked lists, rows and columns.  The _host forms stage their arrays
+ * for the length of the call.  All calls are synchronous on the handle's stream.
+ * Least squares.  sc_normal_lstsq_*_multi minimises
+ *     ||W^1/2 (J x - b)||_2^2 + x^T (C + diag d + lambda I) x
+ * per column of B (m x nrhs) with the factor num holds, which must come from sc_normal_factor_*
+ * on this handle, and from the last such call (SC_ERR_STATE with a message otherwise: the handle
+ * remembers one call's values, C, d and lambda, so a second sc_numeric factored through the
+ * same handle retires the first for this entry point).  Jx and w are passed again and should be the factored ones.  The first iterate is
+ * the plain normal-equations solve x_0 = inv(S) J^T W b, whose error grows with cond(J)^2; then
+ * come corrected semi-normal steps
+ *     r = b - J x,   g = J^T W r - (C + diag d + lambda I) x,   x += inv(S) g
+ * with r and the base product accumulated as opt->residual says (SC_RESIDUAL_DD: compensated),
+ * which bring the error down to what cond(J) allows.  Options, stopping states and rules are
+ * those of sc_solve_refine_*_multi (sc_refine_options; per column: CONVERGED when the increment
+ * falls below u ||x||_inf or the gradient is exactly zero, STALLED when it contracts by less than
+ * rho_max, MAXITER, DIVERGED when it does not contract at all -- that increment is not applied;
+ * a stopped column is never touched again).  max_iter = 0 returns x_0.  sc_lstsq_info (nrhs
+ * entries, host, may be NULL) describes the returned X: grad_norm = ||g||_inf, resid_norm =
+ * ||W^1/2 r||_2 (NaN for negative weights), dx_ratio = the last increment over ||x||_inf.
+ * Status: SC_ERR_STATE before a factorization; a failed factorization returns its status > 0
+ * and writes nothing; X == B and the argument errors of sc_solve_refine_*_multi: SC_ERR_ARG
+ * with a message; multi-rank and emulated handles SC_ERR_NOTIMPL.  In the compensated mode the
+ * residual and the gradient are kept as unevaluated pairs of doubles (as if in twice the working
+ * precision) until the base product is off the gradient, which is then rounded once: with a
+ * gradient in plain fp64 the increments of a problem with a large residual stop contracting at
+ * cond(J)^2 u ||r|| and never reach u ||x||.  Allocated at the first call and kept: 384 (n + m)
+ * bytes of panels (gradient, residual and their 16-wide row-major forms, each as a pair), the
+ * base by rows (20 bytes per mirrored entry of C and per row) and what the first
+ * sc_solve_*_multi allocates. */
+typedef struct sc_normal sc_normal;
+typedef struct sc_lstsq_info {
+    int32_t iters, state;      /* increments applied; SC_REFINE_* */
+    double grad_norm, resid_norm, dx_ratio;
+} sc_lstsq_info;
+int64_t sc_normal_create(int64_t m, int64_t n, const int64_t* Jp, const int32_t* Ji, const int64_t* Cp,
+                         const int32_t* Ci, int32_t device, sc_normal** out);
+void sc_normal_free(sc_normal* normal);
+int64_t sc_normal_pattern(const sc_normal* normal, int64_t* Sp, int32_t* Si);
+int64_t sc_normal_terms(const sc_normal* normal);
+int64_t sc_normal_term_lists(const sc_normal* normal, int64_t* tp, int32_t* pa, int32_t* pb, int32_t* r,
+                             int64_t* cpos);
+int64_t sc_normal_rows(const sc_normal* normal, int64_t* rp, int32_t* ci, int64_t* sp);
+int64_t sc_normal_memory(const sc_normal* normal, int64_t* out, int32_t cap);
+int64_t sc_normal_constants(int32_t* out, int32_t cap);
+int64_t sc_normal_values_host(sc_normal* normal, const double* Jx, const double* w, const double* Cx,
+                              const double* d, double lambda, double* Sx);
+int64_t sc_normal_values_device(sc_normal* normal, const double* d_Jx, const double* d_w, const double* d_Cx,
+                                const double* d_d, double lambda, double* d_Sx);
+int64_t sc_normal_factor_host(sc_normal* normal, sc_numeric* num, const double* Jx, const double* w,
+                              const double* Cx, const double* d, double lambda);
+int64_t sc_normal_factor_device(sc_normal* normal, sc_numeric* num, const double* d_Jx, const double* d_w,
+                                const double* d_Cx, const double* d_d, double lambda);
+const double* sc_normal_values_ptr(const sc_normal* normal);
+int64_t sc_normal_mul_host_multi(sc_normal* normal, int32_t nrhs, const double* Jx, const double* X, int64_t ldx,
+                                 double* Y, int64_t ldy);
+int64_t sc_normal_mul_device_multi(sc_normal* normal, int32_t nrhs, const double* d_Jx, const double* d_X,
+                                   int64_t ldx, double* d_Y, int64_t ldy);
+int64_t sc_normal_mult_host_multi(sc_normal* normal, int32_t nrhs, const double* Jx, const double* w,
+                                  const double* Y, int64_t ldy, double* G, int64_t ldg);
+int64_t sc_normal_mult_device_multi(sc_normal* normal, int32_t nrhs, const double* d_Jx, const double* d_w,
+                                    const double* d_Y, int64_t ldy, double* d_G, int64_t ldg);
+int64_t sc_normal_lstsq_host_multi(sc_normal* normal, sc_numeric* num, const sc_refine_options* opt, int32_t nrhs,
+                                   const double* Jx, const double* w, const double* B, int64_t ldb, double* X,
+                                   int64_t ldx, sc_lstsq_info* info);
+int64_t sc_normal_lstsq_device_multi(sc_normal* normal, sc_numeric* num, const sc_refine_options* opt, int32_t nrhs,
+                                     const double* d_Jx, const double* d_w, const double* d_B, int64_t ldb,
+                                     double* d_X, int64_t ldx, sc_lstsq_info* info);
+
 /* ---------------- reference-API helpers (host) ----------------
  * Each mirrors one reference function, with int64 column pointers. */
 /* etree(A)  chol.hpp:377-410 */

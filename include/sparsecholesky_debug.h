@@ -109,6 +109,39 @@ int64_t sc_debug_schur_llt(const double* dD, int32_t ns, int64_t ldd, double* dS
 int64_t sc_debug_spmv(int32_t mode, int32_t n, const int64_t* rp, const int32_t* ci, const int64_t* sp, int64_t nval,
                       const double* d_Ax, int32_t nrhs, const double* d_X, int64_t ldx, const double* d_B, int64_t ldb,
                       double* d_R, int64_t ldr, double* d_W, int64_t ldw, double* d_norms);
+/* The three kernels of the weighted normal equations alone (no handle) on a caller's
+ * structures: host arrays, validated before anything is launched (pointer arrays ascending
+ * from 0, every position, row and index inside the counts given), values and panels in
+ * device memory.  Synchronous; SC_ERR_ARG with a message in sc_last_error.
+ *   sc_debug_normal_form  d_Sx[e] for the ne entries whose term lists are tp / ta / tb / tr
+ *                         (sc_normal_term_lists), cpos (position in d_Cx or -1) and dcol (the
+ *                         entry's column when it is diagonal, else -1); nJ, nw, nC, nd: the
+ *                         lengths of d_Jx, d_w, d_Cx, d_d (d_w, d_Cx, d_d may be NULL);
+ *   sc_debug_normal_mul   mode 0: R = J X; 1 / 2: R = B - J X in fp64 / compensated, over the
+ *                         row structure rp / ci / sp of m rows, ci in [0, n), sp in [0, nval);
+ *                         X n x nrhs, B and R m x nrhs, nrhs <= 16;
+ *   sc_debug_normal_mult  G = J^T diag(w) Y down the CSC columns Jp / Ji (row indices in [0, m));
+ *                         Y m x nrhs, G n x nrhs, d_w may be NULL.
+ *   sc_debug_normal_pair  the pair path of the least-squares gradient: (R, Rl) = B - J X as the
+ *                         unevaluated pair the compensated residual leaves, over rp / ci / sp,
+ *                         then (G, Gl) = J^T diag(w) (R + Rl) by the pair product down Jp / Ji,
+ *                         as if in twice the working precision; |Rl| <= ulp(R) / 2, likewise Gl.
+ *                         X n x nrhs, B, R, Rl m x nrhs (ldr for both), G, Gl n x nrhs (ldg).
+ * Nothing outside the windows of the outputs is written. */
+int64_t sc_debug_normal_pair(int64_t m, int64_t n, const int64_t* Jp, const int32_t* Ji, const int64_t* rp,
+                             const int32_t* ci, const int64_t* sp, const double* d_Jx, const double* d_w, int32_t nrhs,
+                             const double* d_X, int64_t ldx, const double* d_B, int64_t ldb, double* d_R, double* d_Rl,
+                             int64_t ldr, double* d_G, double* d_Gl, int64_t ldg);
+int64_t sc_debug_normal_form(int64_t ne, const int64_t* tp, const int32_t* ta, const int32_t* tb, const int32_t* tr,
+                             const int64_t* cpos, const int32_t* dcol, int64_t nJ, int64_t nw, int64_t nC, int64_t nd,
+                             const double* d_Jx, const double* d_w, const double* d_Cx, const double* d_d,
+                             double lambda, double* d_Sx);
+int64_t sc_debug_normal_mul(int32_t mode, int64_t m, int64_t n, const int64_t* rp, const int32_t* ci,
+                            const int64_t* sp, int64_t nval, const double* d_Jx, int32_t nrhs, const double* d_X,
+                            int64_t ldx, const double* d_B, int64_t ldb, double* d_R, int64_t ldr);
+int64_t sc_debug_normal_mult(int64_t m, int64_t n, const int64_t* Jp, const int32_t* Ji, const double* d_Jx,
+                             const double* d_w, int32_t nrhs, const double* d_Y, int64_t ldy, double* d_G,
+                             int64_t ldg);
 /* One vector kernel of the conjugate gradients alone (no handle) on caller panels in device
  * memory, n x nrhs column-major, nrhs <= 16, leading dimensions >= n; mask: bit c set = column
  * c takes part (bits >= nrhs are ignored); coef: 16 host doubles, one per column; out: 2 x 16

@@ -50,6 +50,7 @@ __all__ = [
     "SC_REFINE_CONVERGED", "SC_REFINE_STALLED", "SC_REFINE_MAXITER", "SC_REFINE_DIVERGED",
     "PcgOptions", "PcgInfo", "SC_PCG_CONVERGED", "SC_PCG_MAXITER", "SC_PCG_BREAKDOWN",
     "EigsOptions", "EigsInfo", "SC_EIGS_CONVERGED", "SC_EIGS_MAXBLOCKS", "SC_EIGS_EXHAUSTED",
+    "NormalEquations", "LstsqInfo",
 ]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -119,6 +120,11 @@ class EigsOptions(C.Structure):
 
 class EigsInfo(C.Structure):
     _fields_ = [("state", C.c_int32), ("blocks", C.c_int32), ("est", C.c_double), ("resid", C.c_double)]
+
+
+class LstsqInfo(C.Structure):
+    _fields_ = [("iters", C.c_int32), ("state", C.c_int32), ("grad_norm", C.c_double),
+                ("resid_norm", C.c_double), ("dx_ratio", C.c_double)]
 
 
 class SymbolicStats(C.Structure):
@@ -218,6 +224,25 @@ _SIGS = [
     ("sc_logdet_grad_device", _I64, [_P, _P]),
     ("sc_solve_grad_host", _I64, [_P, _I32, _P, _I64, _P, _I64, _P, _I64, _P]),
     ("sc_solve_grad_device", _I64, [_P, _I32, _P, _I64, _P, _I64, _P, _I64, _P]),
+    ("sc_normal_create", _I64, [_I64, _I64, _P, _P, _P, _P, _I32, C.POINTER(_P)]),
+    ("sc_normal_free", None, [_P]),
+    ("sc_normal_pattern", _I64, [_P, _P, _P]),
+    ("sc_normal_terms", _I64, [_P]),
+    ("sc_normal_term_lists", _I64, [_P, _P, _P, _P, _P, _P]),
+    ("sc_normal_rows", _I64, [_P, _P, _P, _P]),
+    ("sc_normal_memory", _I64, [_P, _P, _I32]),
+    ("sc_normal_constants", _I64, [_P, _I32]),
+    ("sc_normal_values_host", _I64, [_P, _P, _P, _P, _P, _D, _P]),
+    ("sc_normal_values_device", _I64, [_P, _P, _P, _P, _P, _D, _P]),
+    ("sc_normal_factor_host", _I64, [_P, _P, _P, _P, _P, _P, _D]),
+    ("sc_normal_factor_device", _I64, [_P, _P, _P, _P, _P, _P, _D]),
+    ("sc_normal_values_ptr", _P, [_P]),
+    ("sc_normal_mul_host_multi", _I64, [_P, _I32, _P, _P, _I64, _P, _I64]),
+    ("sc_normal_mul_device_multi", _I64, [_P, _I32, _P, _P, _I64, _P, _I64]),
+    ("sc_normal_mult_host_multi", _I64, [_P, _I32, _P, _P, _P, _I64, _P, _I64]),
+    ("sc_normal_mult_device_multi", _I64, [_P, _I32, _P, _P, _P, _I64, _P, _I64]),
+    ("sc_normal_lstsq_host_multi", _I64, [_P, _P, C.POINTER(RefineOptions), _I32, _P, _P, _P, _I64, _P, _I64, _P]),
+    ("sc_normal_lstsq_device_multi", _I64, [_P, _P, C.POINTER(RefineOptions), _I32, _P, _P, _P, _I64, _P, _I64, _P]),
     ("sc_etree", _I64, [_I64, _P, _P, _P]),
     ("sc_post_order", _I64, [_I64, _P, _P]),
     ("sc_col_count", _I64, [_I64, _P, _P, _P, _P, _P]),
@@ -248,6 +273,11 @@ _SIGS = [
     ("sc_debug_solve_step", _I64, [_P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P]),
     ("sc_debug_solve_gather", _I64, [_I32, _I32, _I32, _I32, _P, _P, _P, _P, _P]),
     ("sc_debug_spmv", _I64, [_I32, _I32, _P, _P, _P, _I64, _P, _I32, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _P]),
+    ("sc_debug_normal_form", _I64, [_I64, _P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _P, _P, _P, _P, _D, _P]),
+    ("sc_debug_normal_mul", _I64, [_I32, _I64, _I64, _P, _P, _P, _I64, _P, _I32, _P, _I64, _P, _I64, _P, _I64]),
+    ("sc_debug_normal_mult", _I64, [_I64, _I64, _P, _P, _P, _P, _I32, _P, _I64, _P, _I64]),
+    ("sc_debug_normal_pair", _I64, [_I64, _I64, _P, _P, _P, _P, _P, _P, _P, _I32, _P, _I64, _P, _I64, _P, _P, _I64, _P, _P,
+                                    _I64]),
     ("sc_debug_pcg_vec", _I64, [_I32, _I32, _I32, C.c_uint32, _P, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _P]),
     ("sc_debug_eigs_gram", _I64, [_I32, _I32, _I32, _P, _I64, _I64, _P, _I64, _P]),
     ("sc_debug_eigs_update", _I64, [_I32, _I32, _I32, _I32, _D, _P, _I64, _P, _I64, _P, _I64, _I64, _P]),
@@ -1488,6 +1518,278 @@ class Numeric:
         h = getattr(self, "h", None)
         if h and _lib is not None:
             _lib.sc_free_numeric(h)
+            self.h = None
+
+
+class NormalEquations:
+    """The weighted normal equations S = C + J^T diag(w) J + diag(d) + damping I of a
+    rectangular sparse ``J`` (a :class:`csc_matrix`, m x n, ``S = sym.none``), formed and
+    factored on the GPU.  ``base``: the upper-triangular pattern of C as a :class:`csc_matrix`
+    (n x n), or ``None``.  The handle holds structure only: J's values (default: ``J.x``), the
+    weights, C's values and d come with every call.  Pass :meth:`matrix` to :class:`Symbolic`,
+    a :class:`Numeric` of that analysis to :meth:`factor`, and use every solve, refinement,
+    ``logdet`` or gradient of that :class:`Numeric` as usual."""
+
+    def __init__(self, J: csc_matrix, base: Optional[csc_matrix] = None, device: int = -1):
+        self.J = J
+        self.m, self.n = int(J.n_rows), int(J.n_cols)
+        self.base = base
+        if base is not None and (base.n_rows != self.n or base.n_cols != self.n):
+            raise ValueError(f"NormalEquations: the base is {base.n_rows} x {base.n_cols}, J has {self.n} columns")
+        Jp = np.ascontiguousarray(J.p, dtype=np.int64)
+        Ji = np.ascontiguousarray(J.i, dtype=np.int32)
+        Cp = None if base is None else np.ascontiguousarray(base.p, dtype=np.int64)
+        Ci = None if base is None else np.ascontiguousarray(base.i, dtype=np.int32)
+        h = C.c_void_p()
+        _check(lib().sc_normal_create(self.m, self.n, _ptr(Jp), _ptr(Ji), _ptr(Cp), _ptr(Ci), device, C.byref(h)),
+               "normal_create")
+        self.h = h
+        self.nnz = int(Jp[self.n]) if self.n > 0 else 0
+        self.nnz_base = 0 if base is None else int(Cp[self.n]) if self.n > 0 else 0
+        self.nvalues = _check(lib().sc_normal_pattern(self.h, None, None), "normal_pattern")
+
+    @staticmethod
+    def constants() -> dict:
+        """The boundaries between the form kernel's mappings and the products' chunk."""
+        v = np.zeros(4, dtype=np.int32)
+        _check(lib().sc_normal_constants(_ptr(v), 4), "normal_constants")
+        return dict(short=int(v[0]), lanes=int(v[1]), chunk=int(v[2]), product_chunk=int(v[3]))
+
+    def matrix(self) -> csc_matrix:
+        """The pattern of S as an upper :class:`csc_matrix` (values zero), for :class:`Symbolic`."""
+        Sp = np.zeros(self.n + 1, dtype=np.int64)
+        Si = np.zeros(max(self.nvalues, 1), dtype=np.int32)
+        _check(lib().sc_normal_pattern(self.h, _ptr(Sp), _ptr(Si)), "normal_pattern")
+        return csc_matrix(self.n, self.n, Sp, Si[:self.nvalues], np.zeros(self.nvalues), sym.upper)
+
+    @property
+    def terms(self) -> int:
+        return _check(lib().sc_normal_terms(self.h), "normal_terms")
+
+    def term_lists(self) -> tuple:
+        """(tp, pa, pb, r, cpos): entry e of :meth:`matrix` sums the terms [tp[e], tp[e + 1]),
+        term t being J.x[pa[t]] w[r[t]] J.x[pb[t]]; cpos[e]: the entry's position in the base's
+        values, or -1.  Host only."""
+        T = self.terms
+        tp = np.zeros(self.nvalues + 1, dtype=np.int64)
+        pa, pb, r = (np.zeros(max(T, 1), dtype=np.int32) for _ in range(3))
+        cpos = np.zeros(max(self.nvalues, 1), dtype=np.int64)
+        _check(lib().sc_normal_term_lists(self.h, _ptr(tp), _ptr(pa), _ptr(pb), _ptr(r), _ptr(cpos)), "normal_term_lists")
+        return tp, pa[:T], pb[:T], r[:T], cpos[:self.nvalues]
+
+    def rows(self) -> tuple:
+        """J by rows: (rp, ci, sp) with ascending columns ci per row and sp the position of each
+        value in J's value array (sc_normal_rows).  Host only."""
+        rp = np.zeros(self.m + 1, dtype=np.int64)
+        ci = np.zeros(max(self.nnz, 1), dtype=np.int32)
+        sp = np.zeros(max(self.nnz, 1), dtype=np.int64)
+        _check(lib().sc_normal_rows(self.h, _ptr(rp), _ptr(ci), _ptr(sp)), "normal_rows")
+        return rp, ci[:self.nnz], sp[:self.nnz]
+
+    def memory(self) -> dict:
+        v = np.zeros(4, dtype=np.int64)
+        _check(lib().sc_normal_memory(self.h, _ptr(v), 4), "normal_memory")
+        return dict(host_bytes=int(v[0]), device_bytes=int(v[1]), terms=int(v[2]), entries=int(v[3]))
+
+    def _vec(self, a, count: int, what: str):
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if a.shape != (count,):
+            raise ValueError(f"NormalEquations: {what} is {a.shape}, expected ({count},)")
+        return a
+
+    def _form_args(self, Jx, w, base_values, d):
+        Jx = self._vec(self.J.x if Jx is None else Jx, self.nnz, "Jx")
+        return Jx, self._vec(w, self.m, "w"), self._vec(base_values, self.nnz_base, "base_values"), self._vec(d, self.n, "d")
+
+    def values(self, Jx=None, w=None, base_values=None, d=None, damping: float = 0.0) -> np.ndarray:
+        """S's values in the order of :meth:`matrix`, formed on the GPU (sc_normal_values_host)."""
+        Jx, w, cx, d = self._form_args(Jx, w, base_values, d)
+        Sx = np.zeros(self.nvalues, dtype=np.float64)
+        _check(lib().sc_normal_values_host(self.h, _ptr(Jx), _ptr(w), _ptr(cx), _ptr(d), float(damping), _ptr(Sx)),
+               "normal_values")
+        return Sx
+
+    def factor(self, num: "Numeric", Jx=None, w=None, base_values=None, d=None, damping: float = 0.0) -> int:
+        """Forms S into the handle's device buffer and factors it with ``num``; returns the
+        factorization's status (> 0: not positive definite, the failing column + 1)
+        (sc_normal_factor_host)."""
+        Jx, w, cx, d = self._form_args(Jx, w, base_values, d)
+        return _check(lib().sc_normal_factor_host(self.h, num.h, _ptr(Jx), _ptr(w), _ptr(cx), _ptr(d), float(damping)),
+                      "normal_factor")
+
+    @property
+    def values_ptr(self) -> int:
+        """Device address of the values the last :meth:`factor` formed (0 before the first one)."""
+        return int(lib().sc_normal_values_ptr(self.h) or 0)
+
+    def _panel(self, A, rows: int, what: str):
+        one = np.ndim(A) == 1
+        F = np.asfortranarray(np.reshape(A, (-1, 1)) if one else A, dtype=np.float64)
+        if F.ndim != 2 or F.shape[0] != rows:
+            raise ValueError(f"{what}: the array is {np.shape(A)}, expected {rows} rows")
+        return F, one
+
+    def mul(self, X, Jx=None) -> np.ndarray:
+        """Y = J X on the GPU; X (n,) or (n, k) (sc_normal_mul_host_multi)."""
+        Xf, one = self._panel(X, self.n, "mul")
+        Jx = self._vec(self.J.x if Jx is None else Jx, self.nnz, "Jx")
+        k = Xf.shape[1]
+        Y = np.zeros((self.m, k), dtype=np.float64, order="F")
+        _check(lib().sc_normal_mul_host_multi(self.h, k, _ptr(Jx), _ptr(Xf), max(self.n, 1), _ptr(Y), max(self.m, 1)),
+               "normal_mul")
+        return Y[:, 0] if one else Y
+
+    def mul_t(self, Y, w=None, Jx=None) -> np.ndarray:
+        """G = J^T diag(w) Y on the GPU; Y (m,) or (m, k) (sc_normal_mult_host_multi)."""
+        Yf, one = self._panel(Y, self.m, "mul_t")
+        Jx = self._vec(self.J.x if Jx is None else Jx, self.nnz, "Jx")
+        w = self._vec(w, self.m, "w")
+        k = Yf.shape[1]
+        G = np.zeros((self.n, k), dtype=np.float64, order="F")
+        _check(lib().sc_normal_mult_host_multi(self.h, k, _ptr(Jx), _ptr(w), _ptr(Yf), max(self.m, 1), _ptr(G),
+                                               max(self.n, 1)), "normal_mul_t")
+        return G[:, 0] if one else G
+
+    @staticmethod
+    def _lstsq_info(info, k: int, one: bool) -> dict:
+        d = {f: np.array([getattr(info[j], f) for j in range(k)]) for f, _ in LstsqInfo._fields_}
+        return {f: v[0].item() for f, v in d.items()} if one else d
+
+    def lstsq(self, num: "Numeric", B, Jx=None, w=None, max_iter: int = 10, residual: str = "dd",
+              rho_max: float = 0.5) -> tuple:
+        """(X, info): the minimiser of ||W^1/2 (J x - b)||^2 + x^T (C + diag d + damping I) x per
+        column of B ((m,) or (m, k)) with the factor ``num`` holds from :meth:`factor`, whose
+        ``Jx`` and ``w`` should be passed again: the normal-equations solve plus corrected
+        semi-normal steps.  ``info``: iters, state (SC_REFINE_*), grad_norm, resid_norm,
+        dx_ratio per column (scalars for 1-D input) (sc_normal_lstsq_host_multi)."""
+        Bf, one = self._panel(B, self.m, "lstsq")
+        Jx = self._vec(self.J.x if Jx is None else Jx, self.nnz, "Jx")
+        w = self._vec(w, self.m, "w")
+        k = Bf.shape[1]
+        X = np.zeros((self.n, k), dtype=np.float64, order="F")
+        info = (LstsqInfo * max(k, 1))()
+        o = Numeric._refine_options(max_iter, residual, rho_max)
+        st = _check(lib().sc_normal_lstsq_host_multi(self.h, num.h, C.byref(o), k, _ptr(Jx), _ptr(w), _ptr(Bf),
+                                                     max(self.m, 1), _ptr(X), max(self.n, 1), info), "normal_lstsq")
+        if st > 0:
+            raise LibraryError(f"lstsq: S is not positive definite (column {st})")
+        return (X[:, 0] if one else X), self._lstsq_info(info, k, one)
+
+    # ---- device forms: float64 torch tensors on the handle's device ----
+    @staticmethod
+    def _tensor_ptr(t, count, what: str):
+        import torch
+
+        if t is None:
+            return None, None
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64):
+            raise ValueError(f"NormalEquations: {what} must be a float64 tensor on the GPU")
+        t = t.contiguous()
+        if count is not None and tuple(t.shape) != (count,):
+            raise ValueError(f"NormalEquations: {what} is {tuple(t.shape)}, expected ({count},)")
+        return t, C.c_void_p(t.data_ptr())
+
+    @staticmethod
+    def _torch_done(t):
+        # the library works on its own stream and its calls are synchronous: what torch has
+        # queued for the arrays (copies by contiguous(), the zero fill of an output) must be
+        # done before the pointers are handed over
+        import torch
+
+        torch.cuda.current_stream(t.device).synchronize()
+
+    def values_device(self, Jx, w=None, base_values=None, d=None, damping: float = 0.0, out=None):
+        """:meth:`values` with torch tensors; returns (or fills ``out``) a float64 vector on the
+        device, in the order :meth:`Numeric.factor_device` reads (sc_normal_values_device)."""
+        import torch
+
+        Jx, pj = self._tensor_ptr(Jx, self.nnz, "Jx")
+        w, pw = self._tensor_ptr(w, self.m, "w")
+        cx, pc = self._tensor_ptr(base_values, self.nnz_base, "base_values")
+        d, pd = self._tensor_ptr(d, self.n, "d")
+        if out is None:
+            out = torch.zeros(self.nvalues, dtype=torch.float64, device=Jx.device)
+        if not out.is_contiguous():
+            raise ValueError("NormalEquations: out must be contiguous")
+        _, po = self._tensor_ptr(out, self.nvalues, "out")
+        self._torch_done(out)
+        _check(lib().sc_normal_values_device(self.h, pj, pw, pc, pd, float(damping), po), "normal_values_device")
+        return out
+
+    def factor_device(self, num: "Numeric", Jx, w=None, base_values=None, d=None, damping: float = 0.0) -> int:
+        """:meth:`factor` with torch tensors (sc_normal_factor_device)."""
+        Jx, pj = self._tensor_ptr(Jx, self.nnz, "Jx")
+        w, pw = self._tensor_ptr(w, self.m, "w")
+        cx, pc = self._tensor_ptr(base_values, self.nnz_base, "base_values")
+        d, pd = self._tensor_ptr(d, self.n, "d")
+        self._torch_done(Jx)
+        return _check(lib().sc_normal_factor_device(self.h, num.h, pj, pw, pc, pd, float(damping)),
+                      "normal_factor_device")
+
+    def _panel_device(self, A, rows: int, what: str):
+        import torch
+
+        if not (isinstance(A, torch.Tensor) and A.is_cuda and A.dtype == torch.float64):
+            raise ValueError(f"{what}: the panel must be a float64 tensor on the GPU")
+        one = A.ndim == 1
+        A2 = A.reshape(-1, 1) if one else A
+        if A2.ndim != 2 or A2.shape[0] != rows:
+            raise ValueError(f"{what}: the tensor is {tuple(A.shape)}, expected {rows} rows")
+        return A2.t().contiguous(), one  # row c of the copy is column c: column-major memory
+
+    def _product_device(self, transposed: bool, A, Jx, w, what: str):
+        import torch
+
+        nin, nout = (self.m, self.n) if transposed else (self.n, self.m)
+        At, one = self._panel_device(A, nin, what)
+        Jx, pj = self._tensor_ptr(Jx, self.nnz, "Jx")
+        k = At.shape[0]
+        Ot = torch.zeros((k, nout), dtype=torch.float64, device=At.device)
+        pa = C.c_void_p(At.data_ptr() if nin > 0 and k > 0 else None)
+        po = C.c_void_p(Ot.data_ptr() if nout > 0 and k > 0 else None)
+        w, pw = self._tensor_ptr(w if transposed else None, self.m, "w")
+        self._torch_done(Ot)
+        if transposed:
+            _check(lib().sc_normal_mult_device_multi(self.h, k, pj, pw, pa, max(nin, 1), po, max(nout, 1)), what)
+        else:
+            _check(lib().sc_normal_mul_device_multi(self.h, k, pj, pa, max(nin, 1), po, max(nout, 1)), what)
+        return Ot[0] if one else Ot.t()
+
+    def mul_device(self, X, Jx):
+        """:meth:`mul` with torch tensors; returns a column-major (m, k) tensor."""
+        return self._product_device(False, X, Jx, None, "normal_mul_device")
+
+    def mul_t_device(self, Y, Jx, w=None):
+        """:meth:`mul_t` with torch tensors; returns a column-major (n, k) tensor."""
+        return self._product_device(True, Y, Jx, w, "normal_mul_t_device")
+
+    def lstsq_device(self, num: "Numeric", B, Jx, w=None, max_iter: int = 10, residual: str = "dd",
+                     rho_max: float = 0.5) -> tuple:
+        """:meth:`lstsq` with torch tensors; returns (X, info), X a column-major (n, k) tensor."""
+        import torch
+
+        Bt, one = self._panel_device(B, self.m, "normal_lstsq_device")
+        Jx, pj = self._tensor_ptr(Jx, self.nnz, "Jx")
+        w, pw = self._tensor_ptr(w, self.m, "w")
+        k = Bt.shape[0]
+        Xt = torch.zeros((k, self.n), dtype=torch.float64, device=Bt.device)
+        info = (LstsqInfo * max(k, 1))()
+        o = Numeric._refine_options(max_iter, residual, rho_max)
+        self._torch_done(Xt)
+        st = _check(lib().sc_normal_lstsq_device_multi(
+            self.h, num.h, C.byref(o), k, pj, pw, C.c_void_p(Bt.data_ptr() if self.m > 0 and k > 0 else None),
+            max(self.m, 1), C.c_void_p(Xt.data_ptr() if self.n > 0 and k > 0 else None), max(self.n, 1), info),
+            "normal_lstsq_device")
+        if st > 0:
+            raise LibraryError(f"lstsq_device: S is not positive definite (column {st})")
+        return (Xt[0] if one else Xt.t()), self._lstsq_info(info, k, one)
+
+    def __del__(self):
+        h = getattr(self, "h", None)
+        if h and _lib is not None:
+            _lib.sc_normal_free(h)
             self.h = None
 
 

@@ -4,6 +4,7 @@
 #include <algorithm>
 #include <chrono>
 #include <cstring>
+#include <functional>
 #include <initializer_list>
 #include <new>
 #include <string>
@@ -11,6 +12,7 @@
 
 #include "../../include/sparsecholesky.h"
 #include "../../include/sparsecholesky_debug.h"
+#include "normal_ops.hpp"
 #include "numeric.hpp"
 #include "symbolic.hpp"
 
@@ -37,6 +39,9 @@ struct sc_symbolic {
 struct sc_numeric {
     sc::Numeric* N = nullptr;
     const sc_symbolic* sym = nullptr;
+};
+struct sc_normal {
+    sc::Normal* N = nullptr;
 };
 
 static thread_local std::string g_last_error;
@@ -1202,6 +1207,273 @@ int64_t sc_debug_spmv(int32_t mode, int32_t n, const int64_t* rp, const int32_t*
     try {
         return sc::debug_spmv(mode, n, rp, ci, sp, nval, d_Ax, nrhs, d_X, ldx, d_B, ldb, d_R, ldr, d_W, ldw, d_norms,
                               g_last_error);
+    } catch (const std::bad_alloc&) {
+        return SC_ERR_NOMEM;
+    }
+}
+
+// ---- weighted normal equations ----
+static int64_t normal_fail(const char* who, const std::string& what) {
+    g_last_error = std::string(who) + ": " + what;
+    return SC_ERR_ARG;
+}
+
+// runs f, maps bad_alloc and carries the handle's message over
+static int64_t normal_call(sc_normal* h, const std::function<int64_t()>& f) {
+    int64_t rc;
+    h->N->err.clear();  // a failure without a message of its own must not show an earlier one
+    try {
+        rc = f();
+    } catch (const std::bad_alloc&) {
+        return SC_ERR_NOMEM;
+    }
+    if (rc < 0) g_last_error = h->N->err;
+    return rc;
+}
+
+int64_t sc_normal_create(int64_t m, int64_t n, const int64_t* Jp, const int32_t* Ji, const int64_t* Cp,
+                         const int32_t* Ci, int32_t device, sc_normal** out) {
+    if (!out) return normal_fail("sc_normal_create", "null out");
+    *out = nullptr;
+    sc_normal* h = new (std::nothrow) sc_normal();
+    if (!h) return SC_ERR_NOMEM;
+    int64_t rc;
+    std::string err;
+    try {
+        rc = sc::normal_create(m, n, Jp, Ji, Cp, Ci, device, h->N, err);
+    } catch (const std::bad_alloc&) {
+        rc = SC_ERR_NOMEM;
+    }
+    if (rc != SC_OK) {
+        g_last_error = err;
+        delete h;
+        return rc;
+    }
+    *out = h;
+    return SC_OK;
+}
+
+void sc_normal_free(sc_normal* normal) {
+    if (!normal) return;
+    sc::normal_free(normal->N);
+    delete normal;
+}
+
+int64_t sc_normal_pattern(const sc_normal* normal, int64_t* Sp, int32_t* Si) {
+    if (!normal) return normal_fail("sc_normal_pattern", "null handle");
+    const sc::NormalStruct& H = normal->N->H;
+    if (Sp) std::copy(H.Sp.begin(), H.Sp.end(), Sp);
+    if (Si) std::copy(H.Si.begin(), H.Si.end(), Si);
+    return (int64_t)H.Si.size();
+}
+
+int64_t sc_normal_terms(const sc_normal* normal) {
+    if (!normal) return normal_fail("sc_normal_terms", "null handle");
+    return normal->N->H.T;
+}
+
+int64_t sc_normal_term_lists(const sc_normal* normal, int64_t* tp, int32_t* pa, int32_t* pb, int32_t* r,
+                             int64_t* cpos) {
+    if (!normal) return normal_fail("sc_normal_term_lists", "null handle");
+    const sc::NormalStruct& H = normal->N->H;
+    if (tp) std::copy(H.tp.begin(), H.tp.end(), tp);
+    if (pa) std::copy(H.ta.begin(), H.ta.end(), pa);
+    if (pb) std::copy(H.tb.begin(), H.tb.end(), pb);
+    if (r) std::copy(H.tr.begin(), H.tr.end(), r);
+    if (cpos) std::copy(H.cpos.begin(), H.cpos.end(), cpos);
+    return H.T;
+}
+
+int64_t sc_normal_rows(const sc_normal* normal, int64_t* rp, int32_t* ci, int64_t* sp) {
+    if (!normal) return normal_fail("sc_normal_rows", "null handle");
+    const sc::NormalStruct& H = normal->N->H;
+    if (rp) std::copy(H.rp.begin(), H.rp.end(), rp);
+    if (ci) std::copy(H.ci.begin(), H.ci.end(), ci);
+    if (sp) std::copy(H.sp.begin(), H.sp.end(), sp);
+    return H.nnzJ;
+}
+
+int64_t sc_normal_memory(const sc_normal* normal, int64_t* out, int32_t cap) {
+    if (!normal || (!out && cap > 0) || cap < 0) return normal_fail("sc_normal_memory", "null handle or array");
+    return sc::normal_memory(*normal->N, out, cap);
+}
+
+int64_t sc_normal_constants(int32_t* out, int32_t cap) {
+    const int32_t v[4] = {sc::NORMAL_SHORT, sc::NORMAL_LANES, sc::NORMAL_CH, sc::NORMAL_PCH};
+    if ((!out && cap > 0) || cap < 0) return normal_fail("sc_normal_constants", "null array");
+    for (int32_t k = 0; k < cap && k < 4; ++k) out[k] = v[k];
+    return 4;
+}
+
+// the value arrays of a form call: Jx, and Cx where the handle has base entries
+static int64_t normal_value_args(sc_normal* h, const double* Jx, const double* Cx, const char* who) {
+    if (!h) return normal_fail(who, "null handle");
+    const sc::NormalStruct& H = h->N->H;
+    if (H.nnzJ > 0 && !Jx) return normal_fail(who, "null Jx");
+    if (Cx && !H.has_base) return normal_fail(who, "base values given, but the handle was created without a base pattern");
+    return SC_OK;
+}
+
+static int64_t normal_values(sc_normal* h, const double* Jx, const double* w, const double* Cx, const double* d,
+                             double lambda, double* Sx, bool host, const char* who) {
+    int64_t rc = normal_value_args(h, Jx, Cx, who);
+    if (rc != SC_OK) return rc;
+    if (!Sx && !h->N->H.Si.empty()) return normal_fail(who, "null Sx");
+    return normal_call(h, [&] { return sc::normal_values(*h->N, Jx, w, Cx, d, lambda, Sx, host, who); });
+}
+
+int64_t sc_normal_values_host(sc_normal* normal, const double* Jx, const double* w, const double* Cx,
+                              const double* d, double lambda, double* Sx) {
+    return normal_values(normal, Jx, w, Cx, d, lambda, Sx, true, "sc_normal_values_host");
+}
+int64_t sc_normal_values_device(sc_normal* normal, const double* d_Jx, const double* d_w, const double* d_Cx,
+                                const double* d_d, double lambda, double* d_Sx) {
+    return normal_values(normal, d_Jx, d_w, d_Cx, d_d, lambda, d_Sx, false, "sc_normal_values_device");
+}
+
+static int64_t normal_factor(sc_normal* h, sc_numeric* num, const double* Jx, const double* w, const double* Cx,
+                             const double* d, double lambda, bool host, const char* who) {
+    int64_t rc = normal_value_args(h, Jx, Cx, who);
+    if (rc != SC_OK) return rc;
+    if (!num || !num->N) return normal_fail(who, "null numeric handle");
+    return normal_call(h, [&] { return sc::normal_factor(*h->N, *num->N, Jx, w, Cx, d, lambda, host, who); });
+}
+
+int64_t sc_normal_factor_host(sc_normal* normal, sc_numeric* num, const double* Jx, const double* w,
+                              const double* Cx, const double* d, double lambda) {
+    return normal_factor(normal, num, Jx, w, Cx, d, lambda, true, "sc_normal_factor_host");
+}
+int64_t sc_normal_factor_device(sc_normal* normal, sc_numeric* num, const double* d_Jx, const double* d_w,
+                                const double* d_Cx, const double* d_d, double lambda) {
+    return normal_factor(normal, num, d_Jx, d_w, d_Cx, d_d, lambda, false, "sc_normal_factor_device");
+}
+
+const double* sc_normal_values_ptr(const sc_normal* normal) {
+    return (normal && normal->N->values_valid) ? normal->N->Sbuf : nullptr;
+}
+
+static int64_t normal_product(sc_normal* h, bool transposed, int32_t nrhs, const double* Jx, const double* w,
+                              const double* X, int64_t ldx, double* Y, int64_t ldy, bool host, const char* who) {
+    if (!h) return normal_fail(who, "null handle");
+    const sc::NormalStruct& H = h->N->H;
+    const int64_t nin = transposed ? H.m : H.n, nout = transposed ? H.n : H.m;
+    if (nrhs < 0) return normal_fail(who, "nrhs < 0");
+    if (ldx < nin) return normal_fail(who, "leading dimension of the input below its row count");
+    if (ldy < nout) return normal_fail(who, "leading dimension of the output below its row count");
+    if (nrhs > 0 && nout > 0) {
+        if (!Y || (nin > 0 && !X)) return normal_fail(who, "null panel");
+        if (H.nnzJ > 0 && !Jx) return normal_fail(who, "null Jx");
+        if ((const double*)Y == X) return normal_fail(who, "the output aliases the input");
+    }
+    return normal_call(h, [&] { return sc::normal_product(*h->N, transposed, nrhs, Jx, w, X, ldx, Y, ldy, host, who); });
+}
+
+int64_t sc_normal_mul_host_multi(sc_normal* normal, int32_t nrhs, const double* Jx, const double* X, int64_t ldx,
+                                 double* Y, int64_t ldy) {
+    return normal_product(normal, false, nrhs, Jx, nullptr, X, ldx, Y, ldy, true, "sc_normal_mul_host_multi");
+}
+int64_t sc_normal_mul_device_multi(sc_normal* normal, int32_t nrhs, const double* d_Jx, const double* d_X,
+                                   int64_t ldx, double* d_Y, int64_t ldy) {
+    return normal_product(normal, false, nrhs, d_Jx, nullptr, d_X, ldx, d_Y, ldy, false, "sc_normal_mul_device_multi");
+}
+int64_t sc_normal_mult_host_multi(sc_normal* normal, int32_t nrhs, const double* Jx, const double* w,
+                                  const double* Y, int64_t ldy, double* G, int64_t ldg) {
+    return normal_product(normal, true, nrhs, Jx, w, Y, ldy, G, ldg, true, "sc_normal_mult_host_multi");
+}
+int64_t sc_normal_mult_device_multi(sc_normal* normal, int32_t nrhs, const double* d_Jx, const double* d_w,
+                                    const double* d_Y, int64_t ldy, double* d_G, int64_t ldg) {
+    return normal_product(normal, true, nrhs, d_Jx, d_w, d_Y, ldy, d_G, ldg, false, "sc_normal_mult_device_multi");
+}
+
+static int64_t normal_lstsq(sc_normal* h, sc_numeric* num, const sc_refine_options* opt, int32_t nrhs,
+                            const double* Jx, const double* w, const double* B, int64_t ldb, double* X, int64_t ldx,
+                            sc_lstsq_info* info, bool host, const char* who) {
+    if (!h) return normal_fail(who, "null handle");
+    if (!num || !num->N) return normal_fail(who, "null numeric handle");
+    const sc::NormalStruct& H = h->N->H;
+    if (nrhs < 0) return normal_fail(who, "nrhs < 0");
+    if (ldb < H.m) return normal_fail(who, "leading dimension of B below m");
+    if (ldx < H.n) return normal_fail(who, "leading dimension of X below n");
+    if (nrhs > 0 && H.n > 0) {
+        if (!X || (H.m > 0 && !B)) return normal_fail(who, "null B or X");
+        if (H.nnzJ > 0 && !Jx) return normal_fail(who, "null Jx");
+        if ((const double*)X == B) return normal_fail(who, "X aliases B (the steps need B after X exists)");
+    }
+    sc_refine_options o;
+    sc_default_refine_options(&o);
+    if (opt) {
+        if (opt->struct_size != (int32_t)sizeof(sc_refine_options))
+            return normal_fail(who, "sc_refine_options.struct_size does not match this library's "
+                                    "sizeof(sc_refine_options): initialise the options with sc_default_refine_options()");
+        o = *opt;
+    }
+    if (o.max_iter < 0) return normal_fail(who, "max_iter < 0");
+    if (!(o.rho_max > 0.0 && o.rho_max < 1.0)) return normal_fail(who, "rho_max outside (0, 1)");
+    const int64_t rc = residual_mode_arg(o.residual, who);
+    if (rc != SC_OK) return rc;
+    return normal_call(
+        h, [&] { return sc::normal_lstsq(*h->N, *num->N, o, nrhs, Jx, w, B, ldb, X, ldx, info, host, who); });
+}
+
+int64_t sc_normal_lstsq_host_multi(sc_normal* normal, sc_numeric* num, const sc_refine_options* opt, int32_t nrhs,
+                                   const double* Jx, const double* w, const double* B, int64_t ldb, double* X,
+                                   int64_t ldx, sc_lstsq_info* info) {
+    return normal_lstsq(normal, num, opt, nrhs, Jx, w, B, ldb, X, ldx, info, true, "sc_normal_lstsq_host_multi");
+}
+int64_t sc_normal_lstsq_device_multi(sc_normal* normal, sc_numeric* num, const sc_refine_options* opt, int32_t nrhs,
+                                     const double* d_Jx, const double* d_w, const double* d_B, int64_t ldb,
+                                     double* d_X, int64_t ldx, sc_lstsq_info* info) {
+    return normal_lstsq(normal, num, opt, nrhs, d_Jx, d_w, d_B, ldb, d_X, ldx, info, false,
+                        "sc_normal_lstsq_device_multi");
+}
+
+int64_t sc_debug_normal_form(int64_t ne, const int64_t* tp, const int32_t* ta, const int32_t* tb, const int32_t* tr,
+                             const int64_t* cpos, const int32_t* dcol, int64_t nJ, int64_t nw, int64_t nC, int64_t nd,
+                             const double* d_Jx, const double* d_w, const double* d_Cx, const double* d_d,
+                             double lambda, double* d_Sx) {
+    try {
+        g_last_error.clear();
+        return sc::debug_normal_form(ne, tp, ta, tb, tr, cpos, dcol, nJ, nw, nC, nd, d_Jx, d_w, d_Cx, d_d, lambda,
+                                     d_Sx, g_last_error);
+    } catch (const std::bad_alloc&) {
+        return SC_ERR_NOMEM;
+    }
+}
+
+int64_t sc_debug_normal_mul(int32_t mode, int64_t m, int64_t n, const int64_t* rp, const int32_t* ci,
+                            const int64_t* sp, int64_t nval, const double* d_Jx, int32_t nrhs, const double* d_X,
+                            int64_t ldx, const double* d_B, int64_t ldb, double* d_R, int64_t ldr) {
+    try {
+        g_last_error.clear();
+        if (!sp) return normal_fail("sc_debug_normal_mul", "null sp");
+        return sc::debug_normal_prod(false, mode, m, n, rp, ci, sp, nval, d_Jx, nullptr, nrhs, d_X, ldx, d_B, ldb, d_R,
+                                     ldr, g_last_error);
+    } catch (const std::bad_alloc&) {
+        return SC_ERR_NOMEM;
+    }
+}
+
+int64_t sc_debug_normal_mult(int64_t m, int64_t n, const int64_t* Jp, const int32_t* Ji, const double* d_Jx,
+                             const double* d_w, int32_t nrhs, const double* d_Y, int64_t ldy, double* d_G,
+                             int64_t ldg) {
+    try {
+        g_last_error.clear();
+        const int64_t nval = (Jp && n > 0) ? Jp[n] : 0;
+        return sc::debug_normal_prod(true, 0, n, m, Jp, Ji, nullptr, nval, d_Jx, d_w, nrhs, d_Y, ldy, nullptr, 0, d_G,
+                                     ldg, g_last_error);
+    } catch (const std::bad_alloc&) {
+        return SC_ERR_NOMEM;
+    }
+}
+
+int64_t sc_debug_normal_pair(int64_t m, int64_t n, const int64_t* Jp, const int32_t* Ji, const int64_t* rp,
+                             const int32_t* ci, const int64_t* sp, const double* d_Jx, const double* d_w, int32_t nrhs,
+                             const double* d_X, int64_t ldx, const double* d_B, int64_t ldb, double* d_R, double* d_Rl,
+                             int64_t ldr, double* d_G, double* d_Gl, int64_t ldg) {
+    try {
+        g_last_error.clear();
+        return sc::debug_normal_pair(m, n, Jp, Ji, rp, ci, sp, d_Jx, d_w, nrhs, d_X, ldx, d_B, ldb, d_R, d_Rl, ldr, d_G,
+                                     d_Gl, ldg, g_last_error);
     } catch (const std::bad_alloc&) {
         return SC_ERR_NOMEM;
     }
