@@ -1042,7 +1042,11 @@ int64_t sc_numeric_create_dist_dry(const sc_symbolic* sym, int32_t device, int32
                                    sc_numeric** out);
 
 int64_t sc_device_count(void);
-/* Message of the last failing call on this thread. */
+/* Message of the last failing call on this thread: after a call that returned a status < 0 it
+ * reads "<entry point>: <reason>", with sc_status_string's text as the reason where the call has
+ * none of its own, and never shows an earlier call's message.  Calls that return >= 0 (SC_OK, a
+ * count, the not-positive-definite status) leave it as it was.  The pointer is valid until the
+ * next library call on this thread. */
 const char* sc_last_error(void);
 
 #if defined(__GNUC__)
