@@ -92,6 +92,37 @@ int64_t sc_debug_selinv_times(sc_numeric* num, int32_t profile, double* ms);
  * returns the entry count; a failed factorization's status > 0 cannot be told from a
  * count, so check sc_selinv first. */
 int64_t sc_debug_selinv_cols(sc_numeric* num, int64_t j0, int64_t j1, int64_t* cp, int32_t* ri, double* rx);
+/* One step of the selected inversion's recurrence alone (no handle) on block k0 (a multiple of
+ * 128) of a one-front plan whose row list is the identity: nb = min(128, w - k0), k1 = k0 + nb,
+ * K = [k0, k1), R = [k1, m), nr = m - k1, mb = m - w, 1 <= w <= m < 2^20.  dL (the factor) and
+ * dZ are m x w panels (device, column-major, ld = m); dL holds the rows below the block and, in
+ * the block's strict upper triangle, the inverses an sc_debug_solve_step op 0 call stored on the
+ * same buffer (X(i, k), k < i, at row k, column i of the block; the diagonal is L's).  dZii: mb
+ * x mb (ld = mb, both triangles; may be NULL when mb == 0); dW: nr x nb (column-major, ld = nr;
+ * may be NULL when nr == 0).  The tasks are cut as sc_selinv cuts them.
+ *   op 0: W = L_RK X to dW.  Reads the block's diagonal and strict upper triangle and rows R of
+ *         columns K of dL; nothing of dZ and dZii.
+ *   op 1: Z_RK = -Z_RR W to rows R of columns K of dZ and, for the rows p < w of R, mirrored to
+ *         rows K of column p.  Reads dW, rows R of columns [k1, w) of dZ (Z_RR's pivot part,
+ *         straight and transposed) and dZii; nothing of dL, columns K or rows < k1.
+ *   op 2: Z_KK = X^T X - W^T Z_RK to both triangles of rows K x columns K of dZ: one product per
+ *         64 x 64 tile of the lower triangle for nb + nr <= 512, else chunks of 256 terms into a
+ *         partials buffer of the hook's own and a reduction in chunk order.  Reads dW, rows R of
+ *         columns K of dZ and the block's diagonal and strict upper triangle of dL.
+ * Returns the number of workgroups launched (ops 0 and 1: the 64-row tiles; op 2: products plus
+ * reductions); ops 0 and 1 with nr == 0 return SC_OK with no launch.  Everything is validated
+ * before any device call: a null array, k0 >= w, k0 % 128 != 0, another op or sizes outside
+ * the above return SC_ERR_ARG with a message.  Synchronous. */
+int64_t sc_debug_selinv_step(const double* dL, double* dZ, int32_t m, int32_t w, int32_t k0, int32_t op,
+                             const double* dZii, double* dW);
+/* The push of the selected inversion alone (no handle): a child with mbc contribution rows
+ * under a parent front (m, w) whose Z is in dZ (m x w, ld = m) and dZii (mb x mb, mb = m - w;
+ * may be NULL when mb == 0): dOut[a + mbc b] = Zfront[relind[a], relind[b]], read from the lower
+ * triangles alone (element (max, min)).  relind: host, in [0, m), strictly ascending (validated
+ * before any device call, as are the sizes and pointers: SC_ERR_ARG with a message).  dOut (mbc
+ * x mbc, device) must not overlap dZii.  mbc == 0: SC_OK, nothing launched.  Synchronous. */
+int64_t sc_debug_selinv_push(int32_t m, int32_t w, const double* dZ, const double* dZii, int32_t mbc,
+                             const int32_t* relind, double* dOut);
 /* The Schur complement's product kernel alone on caller data (device memory, no handle):
  * dS = dD dD^T for the lower triangle of dD (ns x ns, column-major, ldd, lds >= ns), both
  * triangles of dS written; what dD holds above its diagonal is never used, nothing outside

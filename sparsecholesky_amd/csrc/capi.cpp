@@ -1487,6 +1487,20 @@ int64_t sc_debug_solve_gather(int32_t width, int32_t w, int32_t mb, int32_t nchi
     });
 }
 
+int64_t sc_debug_selinv_step(const double* dL, double* dZ, int32_t m, int32_t w, int32_t k0, int32_t op,
+                             const double* dZii, double* dW) {
+    return guarded(__func__, [&]() -> int64_t {
+        return sc::debug_selinv_step(dL, dZ, m, w, k0, op, dZii, dW, sc::last_error());
+    });
+}
+
+int64_t sc_debug_selinv_push(int32_t m, int32_t w, const double* dZ, const double* dZii, int32_t mbc,
+                             const int32_t* relind, double* dOut) {
+    return guarded(__func__, [&]() -> int64_t {
+        return sc::debug_selinv_push(m, w, dZ, dZii, mbc, relind, dOut, sc::last_error());
+    });
+}
+
 int64_t sc_debug_bench(int32_t which, int32_t M, int32_t K, int32_t reps, int32_t arg, double* tflops) {
     return guarded(__func__, [&]() -> int64_t {
         if (!tflops || M <= 0 || K <= 0 || reps <= 0) return SC_ERR_ARG;

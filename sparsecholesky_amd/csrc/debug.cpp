@@ -1,8 +1,9 @@
 // Debug and microbenchmark hooks (sc_debug_syrk, sc_debug_syrk_ex, sc_debug_panel,
-// sc_debug_updown_block, sc_debug_solve_step, sc_debug_solve_gather, sc_debug_pcg_vec,
-// sc_debug_eigs_gram, sc_debug_eigs_update, sc_debug_bench): the SYRK, panel, update /
-// downdate, solve / factor-product, conjugate-gradient vector and eigensolver panel kernels on
-// caller data, kernel ceilings on synthetic operands.
+// sc_debug_updown_block, sc_debug_solve_step, sc_debug_solve_gather, sc_debug_selinv_step,
+// sc_debug_selinv_push, sc_debug_pcg_vec, sc_debug_eigs_gram, sc_debug_eigs_update,
+// sc_debug_bench): the SYRK, panel, update / downdate, solve / factor-product, selected-
+// inversion, conjugate-gradient vector and eigensolver panel kernels on caller data, kernel
+// ceilings on synthetic operands.
 #include "numeric_impl.hpp"
 
 namespace sc {
@@ -416,6 +417,88 @@ int64_t debug_solve_gather(int width, int w, int mb, int nchild, const int64_t* 
     const hipError_t e2 = hipDeviceSynchronize();
     if (e == hipSuccess && e2 == hipSuccess && mb > 0)
         e = hipMemcpy(dU, u + tot * width, (size_t)mb * wide, hipMemcpyDeviceToDevice);
+    return (e == hipSuccess && e2 == hipSuccess) ? SC_OK : SC_ERR_HIP;
+}
+
+int64_t debug_selinv_step(const double* dL, double* dZ, int m, int w, int k0, int op, const double* dZii, double* dW,
+                          std::string& err) {
+    auto bad = [&](const char* what) {
+        err = std::string("sc_debug_selinv_step: ") + what;
+        return (int64_t)SC_ERR_ARG;
+    };
+    if (m < 1 || m >= (1 << 20) || w < 1 || w > m) return bad("need 1 <= w <= m < 2^20");
+    if (k0 < 0 || k0 >= w || k0 % SOLVE_NB != 0) return bad("k0 is not a multiple of 128 in [0, w)");
+    if (op < 0 || op > 2) return bad("unknown op");
+    const int nb = std::min(SOLVE_NB, w - k0), nr = m - k0 - nb;
+    if (!dL || !dZ || (!dZii && m > w) || (!dW && nr > 0)) return bad("null array");
+    if (op != 2 && nr == 0) return SC_OK;  // no row below the block: W and Z_RK are empty
+    // the block's tasks of the one front, as selinv_build cuts them
+    SelCut cut;
+    int64_t slot = 0;
+    selinv_cut_block(0, w, m, k0, slot, cut);
+    DevArrays A;
+    SelPlan P {};
+    P.sn_start = A.put(std::vector<int32_t> {0, w});
+    P.sn_m = A.put(std::vector<int32_t> {m});
+    P.panel_off = A.put(std::vector<int64_t> {0});
+    P.cb_off = A.put(std::vector<int64_t> {0});
+    P.blk = A.put(std::vector<SelBlk> {SelBlk {0, k0, 0}});
+    P.lpanel = dL;
+    P.zpanel = dZ;
+    P.zii = const_cast<double*>(dZii);  // a step only reads Z_II
+    P.wbuf = dW;
+    P.part = (double*)A.raw((size_t)std::max<int64_t>(slot, 1) * SEL_KT * SEL_KT * sizeof(double));
+    const int2* d_tiles = A.put(cut.tiles);
+    const int4 *d_kk = A.put(cut.kk), *d_red = A.put(cut.red);
+    if (A.rc != SC_OK) return A.rc;
+    const int nt = (int)cut.tiles.size(), nk = (int)cut.kk.size(), nred = (int)cut.red.size();
+    hipError_t e;
+    switch (op) {
+        case 0: e = launch_selinv_w(P, d_tiles, nt, nullptr); break;
+        case 1: e = launch_selinv_zrk(P, d_tiles, nt, nullptr); break;
+        default: e = launch_selinv_zkk(P, d_kk, nk, d_red, nred, nullptr);
+    }
+    const hipError_t e2 = hipDeviceSynchronize();
+    if (e != hipSuccess || e2 != hipSuccess) return SC_ERR_HIP;
+    return op == 2 ? nk + nred : nt;
+}
+
+int64_t debug_selinv_push(int m, int w, const double* dZ, const double* dZii, int mbc, const int32_t* relind,
+                          double* dOut, std::string& err) {
+    auto bad = [&](const char* what) {
+        err = std::string("sc_debug_selinv_push: ") + what;
+        return (int64_t)SC_ERR_ARG;
+    };
+    if (m < 1 || m >= (1 << 20) || w < 1 || w > m) return bad("need 1 <= w <= m < 2^20");
+    if (mbc < 0 || mbc > m) return bad("mbc outside [0, m]");
+    if (mbc == 0) return SC_OK;
+    if (!dZ || (!dZii && m > w) || !relind || !dOut) return bad("null array");
+    for (int a = 0; a < mbc; ++a) {
+        if (relind[a] < 0 || relind[a] >= m) return bad("relind outside [0, m)");
+        if (a > 0 && relind[a] <= relind[a - 1]) return bad("relind is not strictly ascending");
+    }
+    // the kernel addresses the parent's Z_II and the child's both relative to one arena
+    const uintptr_t base = (uintptr_t)(dZii ? dZii : dOut), out = (uintptr_t)dOut;
+    if (base % sizeof(double) != 0 || out % sizeof(double) != 0) return bad("array not aligned to a double");
+    const int64_t off = out >= base ? (int64_t)((out - base) / sizeof(double)) : -(int64_t)((base - out) / sizeof(double));
+    // supernode 0 the child (one pivot, mbc rows below; only its Z_II and relind are looked
+    // at), 1 the parent front (m, w)
+    SelCut cut;
+    selinv_cut_push(0, 1, mbc, cut);
+    DevArrays A;
+    SelPlan P {};
+    P.sn_start = A.put(std::vector<int32_t> {0, 1, 1 + w});
+    P.sn_m = A.put(std::vector<int32_t> {1 + mbc, m});
+    P.panel_off = A.put(std::vector<int64_t> {0, 0});
+    P.cb_off = A.put(std::vector<int64_t> {off, 0});
+    P.rel_ptr = A.put(std::vector<int64_t> {0, mbc});
+    P.relind = A.put(std::vector<int32_t>(relind, relind + mbc));
+    P.zpanel = const_cast<double*>(dZ);  // the push only reads the parent's panel
+    P.zii = (double*)base;
+    const int4* d_push = A.put(cut.push);
+    if (A.rc != SC_OK) return A.rc;
+    const hipError_t e = launch_selinv_push(P, d_push, (int)cut.push.size(), nullptr);
+    const hipError_t e2 = hipDeviceSynchronize();
     return (e == hipSuccess && e2 == hipSuccess) ? SC_OK : SC_ERR_HIP;
 }
 

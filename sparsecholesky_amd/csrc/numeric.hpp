@@ -617,6 +617,15 @@ int64_t debug_updown_block(double* dF, int m, int w, int k0, double* dW, int sig
 int64_t debug_solve_step(double* dF, int m, int w, int k0, int op, int width, double* dC, double* dY, double* dU);
 int64_t debug_solve_gather(int width, int w, int mb, int nchild, const int64_t* rel_ptr, const int32_t* relind,
                            const double* dUc, double* dC, double* dU);
+// One step of the selected inversion on block k0 of a caller's m x w L and Z panels through a
+// one-front plan whose row list is the identity (op 0 W = L_RK X, 1 Z_RK = -Z_RR W with its
+// mirror, 2 Z_KK), cut by selinv_cut_block; returns the workgroups launched.  And the push of
+// one child's Z_II (mbc rows at the parent positions relind, host) out of a parent front (m,
+// w).  include/sparsecholesky_debug.h has the contracts; err: the reason of an SC_ERR_ARG.
+int64_t debug_selinv_step(const double* dL, double* dZ, int m, int w, int k0, int op, const double* dZii, double* dW,
+                          std::string& err);
+int64_t debug_selinv_push(int m, int w, const double* dZ, const double* dZii, int mbc, const int32_t* relind,
+                          double* dOut, std::string& err);
 // Destroys the captured graphs of the solves and operators (they point at one panel pool).
 void numeric_drop_solve_graphs(Numeric& N);
 int64_t debug_syrk(double* dC, int ldc, const double* dA, int lda, int M, int N, int K);

@@ -121,6 +121,20 @@ void solve_cut_front(int32_t s, int w, int m, int k0, int64_t goff, SolveCut& C)
 // selinv.cpp: the Z panel of the current factorization, computed if it is not there (the
 // status rules of numeric_selinv)
 int64_t selinv_ensure(Numeric& N);
+// The task lists of the selected inversion (the W / Z_RK tiles, the Z_KK products, their
+// reductions, the pushes) and how block bi -- the 128-column step k0 of a front of m rows and
+// w > k0 pivots -- adds its tasks to them: one tile per SEL_BM rows below the block; per 64 x
+// 64 tile of the lower triangle of Z_KK (codes 0, 2, 3) one whole product (slot -1) or, for K
+// = nb + nr > SEL_KSPLIT, selinv_kchunks(K) chunk products into consecutive partial slots
+// from `slot` on (advanced) and one reduction.  selinv_cut_push: the 64 x 64 tiles of child
+// c's Z_II (mbc rows) under parent s.  selinv_build, sc_debug_selinv_step and
+// sc_debug_selinv_push cut with them.
+struct SelCut {
+    std::vector<int2> tiles;
+    std::vector<int4> kk, red, push;
+};
+void selinv_cut_block(int bi, int w, int m, int k0, int64_t& slot, SelCut& C);
+void selinv_cut_push(int32_t c, int32_t s, int mbc, SelCut& C);
 
 // refine.cpp: what the products with A, the refinement and the conjugate gradients share
 // a device buffer for the length of one host call

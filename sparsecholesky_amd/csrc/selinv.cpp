@@ -44,14 +44,35 @@ double selinv_flops(const Symbolic& S) {
     return f;
 }
 
+void selinv_cut_block(int bi, int w, int m, int k0, int64_t& slot, SelCut& C) {
+    const int nb = std::min(SOLVE_NB, w - k0), nr = m - k0 - nb;
+    for (int ti = 0; ti * SEL_BM < nr; ++ti) C.tiles.push_back(make_int2(bi, ti));
+    const int nch = selinv_kchunks((int64_t)nb + nr);
+    for (int code : {0, 2, 3}) {  // tiles (0, 0), (1, 0), (1, 1) of the lower triangle
+        if (code && nb <= 64) break;
+        if (nch == 1) {
+            C.kk.push_back(make_int4(bi, code, 0, -1));
+            continue;
+        }
+        C.red.push_back(make_int4(bi, code, (int)slot, nch));
+        for (int c = 0; c < nch; ++c) C.kk.push_back(make_int4(bi, code, c, (int)(slot + c)));
+        slot += nch;
+    }
+}
+
+void selinv_cut_push(int32_t c, int32_t s, int mbc, SelCut& C) {
+    const int nt = (mbc + 63) / 64;
+    for (int tj = 0; tj < nt; ++tj)
+        for (int ti = 0; ti < nt; ++ti) C.push.push_back(make_int4(c, s, ti, tj));
+}
+
 static int64_t selinv_build(Numeric& N) {
     const Symbolic& S = *N.S;
     const RankMem& R = N.R[0];
     std::vector<std::vector<int32_t>> by_level((size_t)S.nlevels);
     for (int32_t s = 0; s < S.ns; ++s) by_level[S.level[s]].push_back(s);
     std::vector<SelBlk> blk;
-    std::vector<int2> tiles;
-    std::vector<int4> kk, red, push;
+    SelCut C;
     int64_t wmax = 1;   // W scratch: the largest step's sum of nr nb
     int64_t smax = 1;   // partial slots of the split Z_KK products: the largest step's
     for (int32_t lev = S.nlevels - 1; lev >= 0; --lev) {
@@ -59,10 +80,10 @@ static int64_t selinv_build(Numeric& N) {
         for (int32_t s : by_level[lev]) maxw = std::max(maxw, S.w(s));
         for (int k0 = (maxw - 1) / SOLVE_NB * SOLVE_NB; k0 >= 0 && maxw > 0; k0 -= SOLVE_NB) {
             Numeric::SelStep st {};
-            st.toff = (int64_t)tiles.size();
-            st.koff = (int64_t)kk.size();
-            st.poff = (int64_t)push.size();
-            st.roff = (int64_t)red.size();
+            st.toff = (int64_t)C.tiles.size();
+            st.koff = (int64_t)C.kk.size();
+            st.poff = (int64_t)C.push.size();
+            st.roff = (int64_t)C.red.size();
             int64_t woff = 0, slot = 0;
             for (int32_t s : by_level[lev]) {
                 const int w = S.w(s), m = S.sn_m[s];
@@ -71,33 +92,18 @@ static int64_t selinv_build(Numeric& N) {
                 const int bi = (int)blk.size();
                 blk.push_back(SelBlk {s, k0, woff});
                 woff += (int64_t)nr * nb;
-                for (int ti = 0; ti * SEL_BM < nr; ++ti) tiles.push_back(make_int2(bi, ti));
-                const int nch = selinv_kchunks((int64_t)nb + nr);
-                for (int code : {0, 2, 3}) {  // tiles (0, 0), (1, 0), (1, 1) of the lower triangle
-                    if (code && nb <= 64) break;
-                    if (nch == 1) {
-                        kk.push_back(make_int4(bi, code, 0, -1));
-                        continue;
-                    }
-                    red.push_back(make_int4(bi, code, (int)slot, nch));
-                    for (int c = 0; c < nch; ++c) kk.push_back(make_int4(bi, code, c, (int)(slot + c)));
-                    slot += nch;
-                }
+                selinv_cut_block(bi, w, m, k0, slot, C);
             }
             wmax = std::max(wmax, woff);
             smax = std::max(smax, slot);
             if (k0 == 0)  // the level is done: its fronts' children get their Z_II
                 for (int32_t s : by_level[lev])
-                    for (int32_t q = S.child_ptr[s]; q < S.child_ptr[s + 1]; ++q) {
-                        const int32_t c = S.child_list[q];
-                        const int nt = (S.mb(c) + 63) / 64;
-                        for (int tj = 0; tj < nt; ++tj)
-                            for (int ti = 0; ti < nt; ++ti) push.push_back(make_int4(c, s, ti, tj));
-                    }
-            st.tcount = (int32_t)((int64_t)tiles.size() - st.toff);
-            st.kcount = (int32_t)((int64_t)kk.size() - st.koff);
-            st.pcount = (int32_t)((int64_t)push.size() - st.poff);
-            st.rcount = (int32_t)((int64_t)red.size() - st.roff);
+                    for (int32_t q = S.child_ptr[s]; q < S.child_ptr[s + 1]; ++q)
+                        selinv_cut_push(S.child_list[q], s, S.mb(S.child_list[q]), C);
+            st.tcount = (int32_t)((int64_t)C.tiles.size() - st.toff);
+            st.kcount = (int32_t)((int64_t)C.kk.size() - st.koff);
+            st.pcount = (int32_t)((int64_t)C.push.size() - st.poff);
+            st.rcount = (int32_t)((int64_t)C.red.size() - st.roff);
             N.sel_steps.push_back(st);
         }
     }
@@ -107,10 +113,10 @@ static int64_t selinv_build(Numeric& N) {
     }
     SelBlk* d_blk = nullptr;
     TRY(upload(N, blk, d_blk));
-    TRY(upload(N, tiles, N.d_seltile));
-    TRY(upload(N, kk, N.d_selkk));
-    TRY(upload(N, red, N.d_selred));
-    TRY(upload(N, push, N.d_selpush));
+    TRY(upload(N, C.tiles, N.d_seltile));
+    TRY(upload(N, C.kk, N.d_selkk));
+    TRY(upload(N, C.red, N.d_selred));
+    TRY(upload(N, C.push, N.d_selpush));
     void* p = nullptr;
     // the Z panel: the panel arena's size, zeroed once (every entry is rewritten by each call)
     TRY(dalloc(N, (size_t)R.panel_total * sizeof(double), p));
