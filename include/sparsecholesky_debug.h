@@ -123,6 +123,38 @@ int64_t sc_debug_selinv_step(const double* dL, double* dZ, int32_t m, int32_t w,
  * x mbc, device) must not overlap dZii.  mbc == 0: SC_OK, nothing launched.  Synchronous. */
 int64_t sc_debug_selinv_push(int32_t m, int32_t w, const double* dZ, const double* dZii, int32_t mbc,
                              const int32_t* relind, double* dOut);
+/* One of the four extend-add implementations alone (no handle) on one parent front of m rows
+ * and w pivots (1 <= w <= m <= 65536, mb = m - w) with nchild prescribed children, taken in
+ * the order given.  Host arrays, all validated before any device call (SC_ERR_ARG with a
+ * message): rel_ptr (nchild + 1) ascending from 0; child q has mbc_q = rel_ptr[q + 1] -
+ * rel_ptr[q] <= m contribution rows at the parent positions relind[rel_ptr[q] ..], each in
+ * [0, m) and strictly ascending within the child; the A entries of pivot column j are a_ptr[j]
+ * .. a_ptr[j + 1] (a_ptr ascending from 0, w + 1 long), entry e at front row a_pos[e] in [j, m)
+ * (no row twice in a column) with the value d_Ax[a_src[e]], a_src in [0, nval).  Device
+ * buffers of the caller: d_Ax (nval doubles); d_child_cb, the children's contribution blocks
+ * back to back, child q mbc_q x mbc_q column-major of which only the lower triangle is read;
+ * d_panel (m x w, ld = m); d_cb (mb x mb, ld = mb; may be NULL when mb == 0).  The one-parent
+ * plan's bounds tables, gather table and tasks are built by the library's own code (symbolic.cpp
+ * block_bounds, schedule.cpp gather_segments_front and asm_block_tasks).
+ *   op 0: assemble_cols_kernel on the 16-column blocks of front columns [0, p0), p0 = w or m;
+ *         p1 = p2 = 0.
+ *   op 1: assemble_tile_kernel likewise on [0, p0); [p1, p2) with 0 <= p1 <= p2 <= m are handed
+ *         to every task as its column limits (both < 0: no limits).  Tasks of blocks outside
+ *         the limits are launched and write nothing.
+ *         Ops 0 and 1 write entry (i, j >= i) of the columns they cover: 0.0, overwritten by the
+ *         A entry if there is one, then += each child's entry in child order.
+ *   op 2: front_small_kernel (one front per workgroup) on the bucket p0 >= m, p0 in {32, 64, 88,
+ *         96, 128}: assembles as above in LDS, factors the w pivots, writes the panel's lower
+ *         trapezoid and the lower triangle of the contribution block.
+ *   op 3: the gathering contribution-block SYRK on the instance (bt = p0, lean = p1, epi = p2) of
+ *         sc_debug_syrk_ex, tag 1: d_cb = sum of the children's entries - A A^T with A = rows [w, m)
+ *         of d_panel, K = w.  d_cb is written, never read; needs mb >= 1; the A entries are unused.
+ * *info (may be NULL but for op 2): the status word, the first failing panel column + 1, or 0.
+ * Synchronous. */
+int64_t sc_debug_extend_add(int32_t op, int32_t m, int32_t w, int32_t nchild, const int64_t* rel_ptr,
+                            const int32_t* relind, const int64_t* a_ptr, const int32_t* a_pos, const int64_t* a_src,
+                            int64_t nval, const double* d_Ax, const double* d_child_cb, double* d_panel, double* d_cb,
+                            int32_t p0, int32_t p1, int32_t p2, int32_t* info);
 /* The Schur complement's product kernel alone on caller data (device memory, no handle):
  * dS = dD dD^T for the lower triangle of dD (ns x ns, column-major, ldd, lds >= ns), both
  * triangles of dS written; what dD holds above its diagonal is never used, nothing outside

@@ -291,6 +291,8 @@ _SIGS = [
     ("sc_debug_selinv_cols", _I64, [_P, _I64, _I64, _P, _P, _P]),
     ("sc_debug_selinv_step", _I64, [_P, _P, _I32, _I32, _I32, _I32, _P, _P]),
     ("sc_debug_selinv_push", _I64, [_I32, _I32, _P, _P, _I32, _P, _P]),
+    ("sc_debug_extend_add", _I64, [_I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _I64, _P, _P, _P, _P, _I32, _I32, _I32,
+                                   C.POINTER(_I32)]),
     ("sc_debug_hwid", _I64, [_I32, _I32, _I32, _P]),
     ("sc_debug_contention", _I64, [_I32, _I32, _I32, _I32, _I32, _I32, _P]),
     ("sc_debug_schedule_digest", _I64, [_P, _I32, _I32, _I32, _P, _I64]),

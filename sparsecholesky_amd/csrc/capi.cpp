@@ -1501,6 +1501,16 @@ int64_t sc_debug_selinv_push(int32_t m, int32_t w, const double* dZ, const doubl
     });
 }
 
+int64_t sc_debug_extend_add(int32_t op, int32_t m, int32_t w, int32_t nchild, const int64_t* rel_ptr,
+                            const int32_t* relind, const int64_t* a_ptr, const int32_t* a_pos, const int64_t* a_src,
+                            int64_t nval, const double* d_Ax, const double* d_child_cb, double* d_panel, double* d_cb,
+                            int32_t p0, int32_t p1, int32_t p2, int32_t* info) {
+    return guarded(__func__, [&]() -> int64_t {
+        return sc::debug_extend_add(op, m, w, nchild, rel_ptr, relind, a_ptr, a_pos, a_src, nval, d_Ax, d_child_cb, d_panel,
+                                    d_cb, p0, p1, p2, info, sc::last_error());
+    });
+}
+
 int64_t sc_debug_bench(int32_t which, int32_t M, int32_t K, int32_t reps, int32_t arg, double* tflops) {
     return guarded(__func__, [&]() -> int64_t {
         if (!tflops || M <= 0 || K <= 0 || reps <= 0) return SC_ERR_ARG;

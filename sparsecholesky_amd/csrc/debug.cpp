@@ -1,9 +1,10 @@
 // Debug and microbenchmark hooks (sc_debug_syrk, sc_debug_syrk_ex, sc_debug_panel,
 // sc_debug_updown_block, sc_debug_solve_step, sc_debug_solve_gather, sc_debug_selinv_step,
-// sc_debug_selinv_push, sc_debug_pcg_vec, sc_debug_eigs_gram, sc_debug_eigs_update,
-// sc_debug_bench): the SYRK, panel, update / downdate, solve / factor-product, selected-
-// inversion, conjugate-gradient vector and eigensolver panel kernels on caller data, kernel
-// ceilings on synthetic operands.
+// sc_debug_selinv_push, sc_debug_extend_add, sc_debug_pcg_vec, sc_debug_eigs_gram,
+// sc_debug_eigs_update, sc_debug_bench): the SYRK, panel, update / downdate, solve / factor-
+// product, selected-inversion, extend-add (the two assembly kernels, the small-front kernel,
+// the gathering CB SYRK), conjugate-gradient vector and eigensolver panel kernels on caller
+// data, kernel ceilings on synthetic operands.
 #include "numeric_impl.hpp"
 
 namespace sc {
@@ -500,6 +501,188 @@ int64_t debug_selinv_push(int m, int w, const double* dZ, const double* dZii, in
     const hipError_t e = launch_selinv_push(P, d_push, (int)cut.push.size(), nullptr);
     const hipError_t e2 = hipDeviceSynchronize();
     return (e == hipSuccess && e2 == hipSuccess) ? SC_OK : SC_ERR_HIP;
+}
+
+int64_t debug_extend_add(int op, int m, int w, int nchild, const int64_t* rel_ptr, const int32_t* relind,
+                         const int64_t* a_ptr, const int32_t* a_pos, const int64_t* a_src, int64_t nval,
+                         const double* dAx, const double* dKids, double* dPanel, double* dCb, int p0, int p1, int p2,
+                         int32_t* info, std::string& err) {
+    auto bad = [&](const char* what) {
+        err = std::string("sc_debug_extend_add: ") + what;
+        return (int64_t)SC_ERR_ARG;
+    };
+    // ---- everything a kernel will index with, checked on the host before any device call ----
+    if (op < 0 || op > 3) return bad("unknown op");
+    if (m < 1 || m > (1 << 16) || w < 1 || w > m) return bad("need 1 <= w <= m <= 65536");
+    if (nchild < 0 || nchild > (1 << 16)) return bad("nchild outside [0, 65536]");
+    if (!rel_ptr || !a_ptr) return bad("null array");
+    if (rel_ptr[0] != 0) return bad("rel_ptr does not start at 0");
+    for (int q = 0; q < nchild; ++q) {
+        if (rel_ptr[q + 1] < rel_ptr[q]) return bad("rel_ptr descends");
+        if (rel_ptr[q + 1] - rel_ptr[q] > m) return bad("a child has more rows than the parent");
+    }
+    const int64_t tot = rel_ptr[nchild];
+    if (tot > 0 && !relind) return bad("null array");
+    int64_t kids_len = 0;
+    for (int q = 0; q < nchild; ++q) {
+        for (int64_t i = rel_ptr[q]; i < rel_ptr[q + 1]; ++i) {
+            if (relind[i] < 0 || relind[i] >= m) return bad("relind outside [0, m)");
+            if (i > rel_ptr[q] && relind[i] <= relind[i - 1]) return bad("relind is not strictly ascending within a child");
+        }
+        const int64_t mbc = rel_ptr[q + 1] - rel_ptr[q];
+        kids_len += mbc * mbc;
+    }
+    if (a_ptr[0] != 0) return bad("a_ptr does not start at 0");
+    for (int j = 0; j < w; ++j)
+        if (a_ptr[j + 1] < a_ptr[j]) return bad("a_ptr descends");
+    const int64_t na = a_ptr[w];
+    if (nval < 0) return bad("nval < 0");
+    if (na > 0 && (!a_pos || !a_src)) return bad("null array");
+    {
+        std::vector<int32_t> seen((size_t)m, -1);
+        for (int j = 0; j < w; ++j)
+            for (int64_t q = a_ptr[j]; q < a_ptr[j + 1]; ++q) {
+                if (a_pos[q] < j || a_pos[q] >= m) return bad("a_pos outside [j, m) of its column j");
+                if (seen[(size_t)a_pos[q]] == j) return bad("a_pos names a position twice in a column");
+                seen[(size_t)a_pos[q]] = j;
+                if (a_src[q] < 0 || a_src[q] >= nval) return bad("a_src outside [0, nval)");
+            }
+    }
+    const int mb = m - w;
+    int ncol = m;
+    bool limited = false;
+    if (op <= 1) {
+        ncol = p0;
+        if (ncol != w && ncol != m) return bad("ncol is neither w nor m");
+        if (op == 0 && (p1 != 0 || p2 != 0)) return bad("cols takes no limits");
+        limited = op == 1 && !(p1 < 0 && p2 < 0);
+        if (limited && (p1 < 0 || p2 < p1 || p2 > m)) return bad("limits are not 0 <= lo <= hi <= m");
+    } else if (op == 2) {
+        if (p0 != 32 && p0 != 64 && p0 != 88 && p0 != 96 && p0 != 128) return bad("maxm is no bucket (32, 64, 88, 96, 128)");
+        if (m > p0) return bad("m above the bucket");
+        if (!info) return bad("null array");
+    } else {
+        if (mb < 1) return bad("gather needs a contribution block (m > w)");
+        if ((p0 != SYRK_BT_SMALL && p0 != SYRK_BT_LARGE) || (p1 != 0 && p1 != 1) || (p1 && p0 != SYRK_BT_SMALL) ||
+            (p2 != 0 && p2 != 1))
+            return bad("no such SYRK instance (bt 64 or 128, lean with 64 only, epi 0 or 1)");
+    }
+    if (!dPanel || (mb > 0 && !dCb) || (kids_len > 0 && !dKids) || (na > 0 && op != 3 && !dAx)) return bad("null array");
+    // the kernels address the children's CBs and the parent's relative to one arena
+    const uintptr_t base = (uintptr_t)(dKids ? (const void*)dKids : (const void*)dCb), out = (uintptr_t)dCb;
+    if (base % sizeof(double) != 0 || out % sizeof(double) != 0 || (uintptr_t)dPanel % sizeof(double) != 0)
+        return bad("array not aligned to a double");
+    const int64_t off = !dCb ? 0
+                             : out >= base ? (int64_t)((out - base) / sizeof(double))
+                                           : -(int64_t)((base - out) / sizeof(double));
+    // supernode 0 the parent front (m, w; internal columns 0 .. w - 1, so that with no post
+    // table a failing pivot reports its panel column + 1), 1 + q child q (one pivot, mbc
+    // rows below; only its CB and relind are looked at), children in the caller's order
+    const int ns = nchild + 1;
+    std::vector<int32_t> sn_start((size_t)ns + 1), sn_m((size_t)ns), child_ptr((size_t)ns + 1, nchild), child_list((size_t)nchild);
+    std::vector<int64_t> panel_off((size_t)ns + 1, 0), cb_off((size_t)ns + 1, 0), relp((size_t)ns + 1, 0);
+    std::vector<int64_t> rb_ptr((size_t)ns + 1, 0), cbk_ptr((size_t)ns + 1, 0), aptr((size_t)(w + nchild) + 1, na);
+    std::vector<int32_t> rel_bnd, col_bnd;
+    sn_start[0] = 0;
+    sn_m[0] = m;
+    child_ptr[0] = 0;
+    cb_off[0] = off;
+    int64_t koff = 0;
+    for (int q = 0; q < nchild; ++q) {
+        const int32_t mbc = (int32_t)(rel_ptr[q + 1] - rel_ptr[q]);
+        sn_start[(size_t)q + 1] = w + q;
+        sn_m[(size_t)q + 1] = 1 + mbc;
+        child_list[(size_t)q] = q + 1;
+        cb_off[(size_t)q + 1] = koff;
+        koff += (int64_t)mbc * mbc;
+        relp[(size_t)q + 1] = rel_ptr[q];
+        block_bounds(relind + rel_ptr[q], mbc, 0, kAsmRows, rel_bnd);
+        block_bounds(relind + rel_ptr[q], mbc, 0, kAsmCols, col_bnd);
+        rb_ptr[(size_t)q + 2] = (int64_t)rel_bnd.size();
+        cbk_ptr[(size_t)q + 2] = (int64_t)col_bnd.size();
+    }
+    sn_start[(size_t)ns] = w + nchild;
+    relp[(size_t)ns] = tot;
+    for (int j = 0; j <= w; ++j) aptr[(size_t)j] = a_ptr[j];
+    DevArrays A;
+    DevPlan P {};
+    P.sn_start = A.put(sn_start);
+    P.sn_m = A.put(sn_m);
+    P.panel_off = A.put(panel_off);
+    P.cb_off = A.put(cb_off);
+    P.child_ptr = A.put(child_ptr);
+    P.child_list = A.put(child_list);
+    P.rel_ptr = A.put(relp);
+    P.relind = A.put(std::vector<int32_t>(relind, relind + tot));
+    P.rb_ptr = A.put(rb_ptr);
+    P.rel_bnd = A.put(rel_bnd);
+    P.cbk_ptr = A.put(cbk_ptr);
+    P.col_bnd = A.put(col_bnd);
+    P.a_ptr = A.put(aptr);
+    P.a_pos = A.put(std::vector<int32_t>(a_pos, a_pos + na));
+    P.a_src = A.put(std::vector<int64_t>(a_src, a_src + na));
+    P.panel_pool = dPanel;
+    P.cb_pool = (double*)base;
+    P.info = (int32_t*)A.raw(sizeof(int32_t));
+    P.post = nullptr;
+    {  // the assembly ends at ncol, as the schedule ends a gathered front's at w
+        std::vector<int32_t> asm_end(sn_m);
+        asm_end[0] = ncol;
+        P.asm_end = A.put(asm_end);
+    }
+    if (A.rc != SC_OK) return A.rc;
+    // the status word armed as a factorization arms it
+    if (hipMemset(P.info, 0x7f, sizeof(int32_t)) != hipSuccess) return SC_ERR_HIP;
+    hipError_t e = hipSuccess;
+    if (op <= 1) {
+        // the front's assembly tasks as the schedule cuts them (front_asm_tasks); limits: the
+        // same [lo, hi) on every task, as a distributed assembly hands one run's
+        std::vector<int2> tasks;
+        for (int cb = 0; cb * ASM_COLS < ncol; ++cb) asm_block_tasks(tasks, 0, cb, m, op == 1);
+        const int2* d_tasks = A.put(tasks);
+        const int2* d_lim = limited ? A.put(std::vector<int2>(tasks.size(), make_int2(p1, p2))) : nullptr;
+        if (A.rc != SC_OK) return A.rc;
+        e = launch_assemble_large(P, d_tasks, (int)tasks.size(), dAx, nullptr, op == 1, d_lim);
+    } else if (op == 2) {
+        const int32_t* d_nodes = A.put(std::vector<int32_t> {0});
+        if (A.rc != SC_OK) return A.rc;
+        e = launch_front_small(P, d_nodes, 1, p0, false, dAx, nullptr);
+    } else {
+        // the CB SYRK of the front as emit_cb_launches makes it: K = w over rows [w, m) of the
+        // panel, the gather table of schedule.cpp's own builder
+        std::vector<int64_t> gblk;
+        std::vector<GSeg> gseg;
+        std::vector<const double*> cbs((size_t)nchild);
+        for (int q = 0; q < nchild; ++q) cbs[(size_t)q] = (const double*)base + cb_off[(size_t)q + 1];
+        gather_segments_front(w, mb, child_list.data(), nchild, relp.data(), relind, P.relind, cbs.data(), gblk, gseg);
+        GemmTask t {};
+        t.C = dCb;
+        t.A = dPanel + w;
+        t.ldc = mb;
+        t.lda = m;
+        t.M = t.N = mb;
+        t.K = w;
+        t.gs = 0;
+        t.gb = 0;
+        t.gw = w;
+        std::vector<int2> tiles;
+        append_tiles(tiles, 0, mb, mb, p0);
+        xcd_order(tiles.data(), (int64_t)tiles.size());
+        GatherTab gt;
+        gt.blk = A.put(gblk);
+        gt.seg = A.put(gseg);
+        gt.info = P.info;
+        const GemmTask* d_task = A.put(std::vector<GemmTask> {t});
+        const int2* d_tiles = A.put(tiles);
+        if (A.rc != SC_OK) return A.rc;
+        e = launch_syrk(d_task, d_tiles, (int)tiles.size(), p0, 1, nullptr, p2, gt, p1 != 0);
+    }
+    const hipError_t e2 = hipDeviceSynchronize();
+    int32_t st = 0;
+    const hipError_t e3 = e2 == hipSuccess ? hipMemcpy(&st, P.info, sizeof(int32_t), hipMemcpyDeviceToHost) : e2;
+    if (e != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) return SC_ERR_HIP;
+    if (info) *info = (st == 0x7f7f7f7f || st <= 0) ? 0 : st;
+    return SC_OK;
 }
 
 // Panel-kernel microbenchmarks on one synthetic front (m = M rows, w = 64):

@@ -68,7 +68,9 @@ __global__ __launch_bounds__(256) void assemble_cols_kernel(DevPlan P, const int
     const int m = P.sn_m[s];
     const int mb = m - w;
     const int j0 = t.y * ASM_COLS;
-    const int j1 = min(m, j0 + ASM_COLS);
+    // a block that straddles the end of the assembled columns stops there: the CB columns
+    // behind it belong to the gathering CB SYRK
+    const int j1 = min(P.asm_end ? min(m, P.asm_end[s]) : m, j0 + ASM_COLS);
     double* panel = P.panel_pool + P.panel_off[s];
     double* cbs = P.cb_pool + P.cb_off[s];
     // zero the lower part of the owned columns: one wave per column
@@ -94,6 +96,7 @@ __global__ __launch_bounds__(256) void assemble_cols_kernel(DevPlan P, const int
         const int jlo = bnd_at(cbnd, t.y, mbc), jhi = bnd_at(cbnd, t.y + 1, mbc);
         for (int jc = jlo + wid; jc < jhi; jc += 4) {
             const int pj = rel[jc];
+            if (pj >= j1) break;  // rel ascends: the child's later columns lie past the block too
             const double* __restrict__ src = cb + (int64_t)jc * mbc;
             double* dst = (pj < w) ? panel + (int64_t)pj * m : cbs + (int64_t)(pj - w) * mb - w;
 #pragma unroll 4
@@ -138,7 +141,8 @@ __global__ __launch_bounds__(256) void assemble_tile_kernel(DevPlan P, const int
     const int j0 = jb * ASM_COLS;
     const int j1 = min(m, j0 + ASM_COLS);
     const int r0 = k * ASM_ROWS, r1 = min(m, r0 + ASM_ROWS);
-    const int2 cl = lim ? lim[blockIdx.x] : make_int2(0, m);  // owned front columns
+    int2 cl = lim ? lim[blockIdx.x] : make_int2(0, m);  // owned front columns
+    if (P.asm_end) cl.y = min(cl.y, P.asm_end[s]);  // the CB columns behind it: the gathering CB SYRK's
     double* panel = P.panel_pool + P.panel_off[s];
     double* cbs = P.cb_pool + P.cb_off[s];
     const int cp0 = P.child_ptr[s], cp1 = P.child_ptr[s + 1];

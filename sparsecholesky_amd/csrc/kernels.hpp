@@ -52,6 +52,9 @@ struct DevPlan {
     double* cb_pool;
     int32_t* info;              // min failing natural column + 1
     const int32_t* post;        // n: internal -> natural column (what a failing pivot reports)
+    // per supernode (or null: every front whole): the front columns [0, asm_end) the large-front
+    // assembly fills -- w where the CB SYRK gathers the contribution block itself, else m
+    const int32_t* asm_end;
 };
 
 // One child's share of one 64 x 64 block (rb, cb) of a parent's contribution block

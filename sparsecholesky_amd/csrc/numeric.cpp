@@ -219,6 +219,12 @@ int64_t numeric_init(Numeric& N, const Symbolic& S, int device) {
 
     SchedBuild B;
     if ((rc = build_schedule(N, B))) return rc;
+    for (RankMem& R : N.R)
+        if (!R.asm_end.empty()) {
+            int32_t* de = nullptr;
+            if ((rc = upload(N, R.asm_end, de))) return rc;
+            R.P.asm_end = de;
+        }
     CommBuild& cbld = B.cb;
     // multi-rank: packed staging slots of the hosted ranks' messages
     if (cbld.stage_total > 0 && (rc = dalloc(N, (size_t)cbld.stage_total * sizeof(double), p))) return rc;

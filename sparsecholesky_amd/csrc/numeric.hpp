@@ -121,7 +121,10 @@ struct RankMem {
     int64_t panel_total = 0;     // doubles (incl. the PNB tail the TRSM reads past)
     int64_t work_total = 0;      // doubles: high-water mark of the interval plan
     int64_t work_live_max = 0;   // doubles: max over levels of the live region sizes (lower bound)
-    DevPlan P {};                // pools + device copies of panel_off / cb_off
+    // per supernode, or empty (every front whole): the front columns [0, asm_end) this rank's
+    // large-front assembly fills (schedule.cpp emit_assembly; DevPlan.asm_end)
+    std::vector<int32_t> asm_end;
+    DevPlan P {};                // pools + device copies of panel_off / cb_off / asm_end
 };
 // Plan rank `rank`'s regions (D == nullptr: single device, every front here);
 // `placed` (optional) receives every work-arena region with its lifetime.
@@ -626,6 +629,17 @@ int64_t debug_selinv_step(const double* dL, double* dZ, int m, int w, int k0, in
                           std::string& err);
 int64_t debug_selinv_push(int m, int w, const double* dZ, const double* dZii, int mbc, const int32_t* relind,
                           double* dOut, std::string& err);
+// One of the four extend-add implementations on one parent front (m, w) with prescribed
+// children and A entries (host index arrays, validated; device values), through a one-parent
+// plan whose bounds, gather table and tasks come from block_bounds, gather_segments_front and
+// asm_block_tasks: op 0 assemble_cols_kernel (p0 = ncol), 1 assemble_tile_kernel (p0 = ncol,
+// [p1, p2) = the tasks' column limits or both < 0), 2 front_small_kernel (p0 = the bucket), 3
+// the gathering CB SYRK (p0 = bt, p1 = lean, p2 = epi).  *info: the status word (failing panel
+// column + 1, or 0).  include/sparsecholesky_debug.h has the contract.
+int64_t debug_extend_add(int op, int m, int w, int nchild, const int64_t* rel_ptr, const int32_t* relind,
+                         const int64_t* a_ptr, const int32_t* a_pos, const int64_t* a_src, int64_t nval,
+                         const double* dAx, const double* dKids, double* dPanel, double* dCb, int p0, int p1, int p2,
+                         int32_t* info, std::string& err);
 // Destroys the captured graphs of the solves and operators (they point at one panel pool).
 void numeric_drop_solve_graphs(Numeric& N);
 int64_t debug_syrk(double* dC, int ldc, const double* dA, int lda, int M, int N, int K);

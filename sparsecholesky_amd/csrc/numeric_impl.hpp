@@ -98,6 +98,19 @@ void set_pool_bases(Numeric& N, double* pbase, double* wbase);
 // limits for every assembly task.  B is then what numeric_init uploads.
 void finish_build(Numeric& N, SchedBuild& B, double* staging);
 SchedDigest schedule_digest(const Numeric& N, const SchedBuild& B);
+// The extend-add tables of one parent front (w pivots, mb CB rows), which the schedule and
+// sc_debug_extend_add build alike.  gather_segments_front: the CB SYRK's gather table -- per
+// 64 x 64 block (rb, cbk <= rb) of the CB one entry of gblk (the block's first segment) and,
+// in child-list order (the order the entries are added in), one GSeg per child kids[q] with CB
+// rows and columns in the block, then the closing entry; rel_ptr / relind: the host's relative
+// indices, d_relind their device copy, cb[q] the device CB of child q (null: not resident;
+// its segments are left out and the result is false).  asm_block_tasks: the assembly tasks of
+// 16-column block cb of front s (m rows): one task (column streaming), or one per 256-row
+// tile from the block's diagonal tile down (write-once tiles).
+bool gather_segments_front(int w, int mb, const int32_t* kids, int nkids, const int64_t* rel_ptr,
+                           const int32_t* relind, const int32_t* d_relind, const double* const* cb,
+                           std::vector<int64_t>& gblk, std::vector<GSeg>& gseg);
+void asm_block_tasks(std::vector<int2>& out, int32_t s, int cb, int m, bool tiled);
 
 // solve.cpp
 // What every solve starts with: the whole factor in gpanel, the solve plan built.

@@ -61,6 +61,44 @@ void xcd_order_tasks(int2* tiles, int64_t n, const GemmTask* tasks, int ntasks) 
     for (int64_t b = 0; b < n; ++b) tiles[b] = per[b % 8][b / 8];
 }
 
+bool gather_segments_front(int w, int mb, const int32_t* kids, int nkids, const int64_t* rel_ptr,
+                           const int32_t* relind, const int32_t* d_relind, const double* const* cb,
+                           std::vector<int64_t>& gblk, std::vector<GSeg>& gseg) {
+    const int nb = (mb + 63) / 64;
+    bool resident = true;
+    for (int rb = 0; rb < nb; ++rb)
+        for (int cbk = 0; cbk <= rb; ++cbk) {
+            gblk.push_back((int64_t)gseg.size());
+            for (int q = 0; q < nkids; ++q) {
+                const int32_t c = kids[q];
+                const int32_t* rel = relind + rel_ptr[c];
+                const int mbc = (int)(rel_ptr[c + 1] - rel_ptr[c]);
+                auto at = [&](int x) { return (int)(std::lower_bound(rel, rel + mbc, w + x) - rel); };
+                GSeg g {};
+                g.ilo = at(64 * rb);
+                g.ihi = at(std::min(mb, 64 * rb + 64));
+                g.jlo = at(64 * cbk);
+                g.jhi = at(std::min(mb, 64 * cbk + 64));
+                if (g.ilo >= g.ihi || g.jlo >= g.jhi) continue;
+                if (!cb[q]) {
+                    resident = false;
+                    continue;
+                }
+                g.cb = cb[q];
+                g.rel = d_relind + rel_ptr[c];
+                g.mbc = mbc;
+                gseg.push_back(g);
+            }
+        }
+    gblk.push_back((int64_t)gseg.size());
+    return resident;
+}
+
+void asm_block_tasks(std::vector<int2>& out, int32_t s, int cb, int m, bool tiled) {
+    if (!tiled) return out.push_back(make_int2(s, cb));
+    for (int k = cb * ASM_COLS / ASM_ROWS; k * ASM_ROWS < m; ++k) out.push_back(make_int2(s, (k << 16) | cb));
+}
+
 namespace {
 
 // LDS edge of a small front's launch.  88: the widest front whose 4 x 4 tiles fit one
@@ -439,45 +477,24 @@ struct ScheduleBuilder {
     // block of its CB, every child with CB rows and columns in the block, in child order
     // (the order the entries are added in); returns the task's offset in B.gblk
     int64_t gather_segments(int32_t s, int v) {
-        const int w = S.w(s), mb = S.mb(s), nb = (mb + 63) / 64;
         const int64_t gb = (int64_t)B.gblk.size();
         const RankMem& R = N.R[v];
-        for (int rb = 0; rb < nb; ++rb)
-            for (int cbk = 0; cbk <= rb; ++cbk) {
-                B.gblk.push_back((int64_t)B.gseg.size());
-                for (int32_t q = S.child_ptr[s]; q < S.child_ptr[s + 1]; ++q) {
-                    const int32_t c = S.child_list[q];
-                    const int32_t* rel = S.relind.data() + S.rel_ptr[c];
-                    const int mbc = (int)(S.rel_ptr[c + 1] - S.rel_ptr[c]);
-                    auto at = [&](int x) { return (int)(std::lower_bound(rel, rel + mbc, w + x) - rel); };
-                    GSeg g {};
-                    g.ilo = at(64 * rb);
-                    g.ihi = at(std::min(mb, 64 * rb + 64));
-                    g.jlo = at(64 * cbk);
-                    g.jhi = at(std::min(mb, 64 * cbk + 64));
-                    if (g.ilo >= g.ihi || g.jlo >= g.jhi) continue;
-                    if (R.cb_off[c] < 0) {  // the memory plan keeps every gathered child's CB here
-                        N.err = "schedule: gathered child CB not resident on its parent's rank";
-                        continue;
-                    }
-                    g.cb = R.P.cb_pool + R.cb_base(S, c);
-                    g.rel = R.P.relind + S.rel_ptr[c];
-                    g.mbc = mbc;
-                    B.gseg.push_back(g);
-                }
-            }
-        B.gblk.push_back((int64_t)B.gseg.size());
+        const int32_t* kids = S.child_list.data() + S.child_ptr[s];
+        const int nkids = S.child_ptr[s + 1] - S.child_ptr[s];
+        std::vector<const double*> cb((size_t)nkids);  // null: not resident on this rank
+        for (int q = 0; q < nkids; ++q)
+            cb[(size_t)q] = R.cb_off[kids[q]] < 0 ? nullptr : R.P.cb_pool + R.cb_base(S, kids[q]);
+        // the memory plan keeps every gathered child's CB here
+        if (!gather_segments_front(S.w(s), S.mb(s), kids, nkids, S.rel_ptr.data(), S.relind.data(), R.P.relind,
+                                   cb.data(), B.gblk, B.gseg))
+            N.err = "schedule: gathered child CB not resident on its parent's rank";
         return gb;
     }
 
     // ---- assembly ----
     // The assembly tasks of 16-column block cb of front s: one task (column-streaming),
     // or one per 256-row tile from the block's diagonal tile down (write-once tiles).
-    void asm_block_tasks(int32_t s, int cb, bool tiled) {
-        if (!tiled) return B.asmv.push_back(make_int2(s, cb));
-        for (int k = cb * ASM_COLS / ASM_ROWS; k * ASM_ROWS < S.sn_m[s]; ++k)
-            B.asmv.push_back(make_int2(s, (k << 16) | cb));
-    }
+    void asm_block_tasks(int32_t s, int cb, bool tiled) { sc::asm_block_tasks(B.asmv, s, cb, S.sn_m[s], tiled); }
     void front_asm_tasks(int32_t s, int ncol, bool tiled) {
         for (int cb = 0; cb * ASM_COLS < ncol; ++cb) asm_block_tasks(s, cb, tiled);
     }
@@ -513,8 +530,13 @@ struct ScheduleBuilder {
         for (int tiled = 1; tiled >= 0; --tiled) {
             const int64_t off = (int64_t)B.asmv.size();
             for (int32_t s : large)
-                if (asm_tiled(S.sn_m[s]) == (tiled == 1) && !is_dasm(s))
+                if (asm_tiled(S.sn_m[s]) == (tiled == 1) && !is_dasm(s)) {
                     front_asm_tasks(s, gathers(s, v) ? S.w(s) : S.sn_m[s], tiled == 1);
+                    if (gathers(s, v)) {  // the block that straddles column w stops there
+                        if (N.R[v].asm_end.empty()) N.R[v].asm_end = S.sn_m;
+                        N.R[v].asm_end[s] = S.w(s);
+                    }
+                }
             push_range_launch(L_ASM, tiled ? ASM_TILED : ASM_BY_COLS, lev, v, off, B.asmv.size());
         }
         // distributed assembly of a split front: the owner assembles its panel columns,

@@ -181,6 +181,20 @@ static bool validate(i64 n, const i64* Ap, const i32* Ai, std::string& err) {
     return true;
 }
 
+// g(k) = first CB row of a child (relative indices rel, mbc of them, ascending) whose
+// parent position is >= base + k * blk, appended compactly over the blocks the child
+// touches: [k_lo, k_hi, g(k_lo), g(k_lo + 1) .. g(k_hi - 1)] (g = g(k_lo) below k_lo, mbc
+// from k_hi; kernels.hip bnd_at)
+void block_bounds(const i32* rel, i32 mbc, i32 base, int blk, std::vector<i32>& out) {
+    const i32 j0 = (i32)(std::lower_bound(rel, rel + mbc, base) - rel);
+    const i32 klo = j0 < mbc ? (rel[j0] - base) / blk : 0;
+    const i32 khi = j0 < mbc ? (rel[mbc - 1] - base) / blk + 1 : 0;
+    out.push_back(klo);
+    out.push_back(khi);
+    out.push_back(j0);
+    for (i32 k = klo + 1; k < khi; ++k) out.push_back((i32)(std::lower_bound(rel, rel + mbc, base + blk * k) - rel));
+}
+
 i64 analyze(i64 n, const i64* Ap, const i32* Ai, const sc_options& opt, Symbolic& S,
             std::string& err) {
     if (!validate(n, Ap, Ai, err)) return SC_ERR_ARG;
@@ -429,28 +443,15 @@ i64 analyze(i64 n, const i64* Ap, const i32* Ai, const sc_options& opt, Symbolic
     }
     S.relind.resize((size_t)S.rel_ptr[ns]);
     // per child, bounds of its CB rows by blocks of the parent front (the large-front
-    // assembly and the CB SYRK's gather read them instead of binary-searching relind):
-    // g(k) = first CB row whose parent position is >= base + k * blk, stored compactly
-    // over the blocks the child touches: [k_lo, k_hi, g(k_lo), g(k_lo + 1) .. g(k_hi - 1)]
-    // (g = g(k_lo) below k_lo, mbc from k_hi; kernels.hip bnd_at)
+    // assembly and the CB SYRK's gather read them instead of binary-searching relind)
     auto bounds = [&](std::vector<i64>& ptr, std::vector<i32>& out, int blk, bool cb_only) {
         ptr.assign((size_t)ns + 1, 0);
         out.clear();
         for (i32 s = 0; s < ns; ++s) {
             const i32 p = S.sn_parent[s];
-            if (p >= 0) {
-                const i32 base = cb_only ? S.w(p) : 0;
-                const i32* rel = S.relind.data() + S.rel_ptr[s];
-                const i32 mbc = (i32)(S.rel_ptr[s + 1] - S.rel_ptr[s]);
-                const i32 j0 = (i32)(std::lower_bound(rel, rel + mbc, base) - rel);
-                const i32 klo = j0 < mbc ? (rel[j0] - base) / blk : 0;
-                const i32 khi = j0 < mbc ? (rel[mbc - 1] - base) / blk + 1 : 0;
-                out.push_back(klo);
-                out.push_back(khi);
-                out.push_back(j0);
-                for (i32 k = klo + 1; k < khi; ++k)
-                    out.push_back((i32)(std::lower_bound(rel, rel + mbc, base + blk * k) - rel));
-            }
+            if (p >= 0)
+                block_bounds(S.relind.data() + S.rel_ptr[s], (i32)(S.rel_ptr[s + 1] - S.rel_ptr[s]), cb_only ? S.w(p) : 0,
+                             blk, out);
             ptr[s + 1] = (i64)out.size();
         }
     };

@@ -109,6 +109,11 @@ struct Symbolic {
 i64 analyze(i64 n, const i64* Ap, const i32* Ai, const sc_options& opt, Symbolic& S,
             std::string& err);
 
+// One child's compact block bounds (the records of rel_bnd / col_bnd / tile_bnd) appended to
+// out: rel its mbc ascending relative indices, base the parent position block 0 starts at,
+// blk the block size.  analyze and sc_debug_extend_add build their tables with it.
+void block_bounds(const i32* rel, i32 mbc, i32 base, int blk, std::vector<i32>& out);
+
 // Fill-reducing ordering (ordering.cpp): nested dissection by level structures,
 // perm[new] = old; and B = P A P^T as upper CSC with src[q] = A-index of entry q.
 i64 nd_order(i64 n, const i64* Ap, const i32* Ai, i32* perm);
